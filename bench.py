@@ -10,6 +10,12 @@ its own 4096 environments (weak scaling) and the per-step observation all-gather
 inside the timed region.
 
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line (value, ms_per_step, the workload).  Everything
+else -- the CPU-oracle baseline, per-kernel and roofline figures, contact and overflow counts, the other BASELINE configurations,
+the exact-solver and 2,000-step companions of the headline -- runs only with --full.  --dump-outputs DIR writes what the last timed
+step returned (obs, reward, done, info; with --gpus N also the gathered whole-batch record) as float32 .npy files: the inputs are
+seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -51,6 +57,22 @@ MULTI_GPU_CONFIGS = {      # world size -> (key in "configs", --task, timed step
     4: ('config4_ScratchItchPR2Human-v1_16384_envs_4gpu', 'scratchitch', 300),
     8: ('config5_DressingBaxter-v1_32768_envs_8gpu', 'dressing', 30),
 }
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array (float32; float64 stays float64).  Above DUMP_LIMIT_BYTES in all, every array keeps the
+    same share of its rows, picked by a fixed seed and written beside it as <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    share = min(1.0, DUMP_LIMIT_BYTES / float(sum(v.nbytes + 8 * len(v) for v in arrays.values())))     # (+ the row indices, if it comes to that)
+    for k, v in arrays.items():
+        if share < 1.0:
+            rows = np.sort(np.random.RandomState(0).choice(len(v), int(len(v) * share), replace=False))
+            np.save(os.path.join(path, k + '_rows.npy'), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(path, k + '.npy'), v)
 
 
 def _cpu_worker(path, seed, n_steps, model='feeding_jaco'):
@@ -328,6 +350,8 @@ def dry_run(args, rank, world):
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(obs=o, reward=r, done=d, info=i, **({'gathered_record': full} if world > 1 else {})))
     gi, od = torch.arange(world * n, dtype=torch.float32), blob.obs_dim
     # every rank holds the whole batch in global env order, every column of the record where it belongs
     ok = bool(torch.equal(full[:, od - 1], gi) and torch.equal(full[:, od], -gi) and torch.equal(full[:, od + 1], (gi.long() % 2).float()) and
@@ -339,8 +363,9 @@ def dry_run(args, rank, world):
             'dry_run': True}
 
 
-def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, cpu=True, workload=None, env_id_override=None):
-    """one timed run of one configuration on this rank's GPU; returns the JSON-able dict on rank 0 (None elsewhere)"""
+def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, cpu=True, workload=None, env_id_override=None, dump=None):
+    """one timed run of one configuration on this rank's GPU; returns the JSON-able dict on rank 0 (None elsewhere).  Without args.full
+    only the timed steps and the headline fields; dump: directory for the outputs of the last timed step (dump_outputs)"""
     import torch
     import torch.distributed as dist
     from assistive_gym_amd import vec_env
@@ -425,8 +450,8 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
             gatherer.pack(k & 1, env.obs, env.reward, env.done, env.info)
             gatherer.submit(k & 1)
 
-    # the contact sampling of the timed loop (torch remainder / cast / mean / add kernels and their allocations) runs in the warm-up too:
-    # the first call of each loads its code object (tens of ms each) -- inside a 20-step timed window that was half of the time
+    # --full: the contact sampling of the timed loop (torch remainder / cast / mean / add kernels and their allocations) runs in the warm-up
+    # too: the first call of each loads its code object (tens of ms each) -- inside a 20-step timed window that was half of the time
     # (236 k in the driver's 20-step run vs 471 k over 2,000 steps)
     ncon_sum, ncon_buf = torch.zeros((), device='cuda', dtype=torch.float64), torch.zeros((), device='cuda', dtype=torch.float64)
 
@@ -436,24 +461,28 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
 
     for k in range(W):
         one(k)
+        if args.full:
+            sample_contacts()
+    if args.full:
         sample_contacts()
-    sample_contacts()
-    ncon_sum.zero_()
+        ncon_sum.zero_()
     if distributed:
         gatherer.wait()
     stream = torch.cuda.current_stream().cuda_stream
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
-    overflow0 = env.stepper.overflow_count()
-    env.stepper.profile_begin(stream)
+    if args.full:
+        overflow0 = env.stepper.overflow_count()
+        env.stepper.profile_begin(stream)
     t0 = time.perf_counter()
     ncon_n = 0
     for k in range(W, W + K):
         one(k)
-        if (k - W) % 16 == 0:            # contacts of the last substep, sampled (device-side sum, no host sync)
+        if args.full and (k - W) % 16 == 0:   # contacts of the last substep, sampled (device-side sum, no host sync)
             sample_contacts(); ncon_n += 1
-    kernel_ms = env.stepper.profile_end(stream)
+    if args.full:
+        kernel_ms = env.stepper.profile_end(stream)
     if distributed:
         gatherer.wait()                  # the last gathers are inside the timed region
         dist.barrier()
@@ -478,10 +507,30 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
         okt = torch.tensor([1 if ok else 0], device='cuda', dtype=torch.int32)
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         in_order = bool(okt.item())
-    overflow = env.stepper.overflow_count() - overflow0
+    if dump and rank == 0:
+        dump_outputs(dump, dict(obs=env.obs, reward=env.reward, done=env.done, info=env.info,
+                                **({'gathered_record': gatherer.full[(W + K - 1) & 1]} if distributed else {})))
     if comm is not None:
         from assistive_gym_amd import libagx
         torch.cuda.synchronize(); libagx.comm_destroy(comm)
+    out = None
+    if rank == 0:
+        value = world * n * K / elapsed
+        out = {
+            'metric': 'env_steps_per_sec', 'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'steps': K, 'warmup': W,
+            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
+            'data': 'synthetic',
+            'config': {'workload': '%s, %d lockstep envs per MI355X, %s, 5 simulation steps per env step, %d PGS sweeps' % (env_id, n, 'random-policy rollout' if workload is None else ('scripted press-and-wipe policy on the device (tool force feedback), whole 200-step episodes from starts with the pad on the arm; the pad carries force in %.0f %% of the selection rollout' % (100 * dense_touching)) if workload == 'dense' else 'pad pressed onto the arm at every reset, 8-step episodes, small random actions (x%.2f)' % action_scale, int(blob.param('NITER'))),
+                       'envs_per_gpu': n, 'global_envs': world * n, 'reset_pool': pool, 'reset': args.reset, 'parallelism': 'env-sharded x%d' % world,
+                       'obs_allgather': bool(distributed), 'gather': gather_how, 'gathered_record': 'obs | reward | done | total_force_on_human | task_success' if distributed else None,
+                       'gathered_in_global_order': in_order, 'noop_retest': blob.param('NOOP_RETEST'),
+                       **({'ranks_share_gpus': '%d ranks on %d device(s): a rehearsal of the N-rank command (--share-gpus), not a scaling point' % (world, torch.cuda.device_count())} if getattr(args, 'share_gpus', False) else {})},
+            'pool_states_refreshed': int(getattr(env, 'pool_refreshed', 0)),      # --pool-refresh: start states a child process sampled during the run and the rollout swapped into the pool
+        }
+    if not args.full:
+        env.close()
+        return out
+    overflow = env.stepper.overflow_count() - overflow0
     contacts = float(ncon_sum.item()) / max(1, ncon_n)
     # per-kernel launch durations (HIP events after every launch, on the chunk stream it is launched on),
     # measured after the timed region so that `value` is not perturbed by the extra events / host syncs.
@@ -501,10 +550,7 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
             ms, cnt = env.stepper.step_timed(act, env.obs, env.reward, env.done, env.info, stream)
             kms += np.array(ms); kcnt += np.array(cnt)
         kms /= NT; kcnt /= NT
-    out = None
     if rank == 0:
-        total_steps = world * n * K
-        value = total_steps / elapsed
         sw = blob.state_words
         # algorithmic HBM bytes per env-step: state record read + written once, action read, obs /
         # reward / done / info written (DESIGN.md "bytes per env-step")
@@ -551,18 +597,9 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
                     if traffic_key:
                         cloth_kernel = dict(kernel=traffic_key, **{k: kj[k] for k in kj if k != 'hbm_bytes_per_env_launch'}, hbm_bytes_per_env_launch=kj['hbm_bytes_per_env_launch'])
                     break
-        out = {
-            'metric': 'env_steps_per_sec', 'value': value, 'unit': 'env-steps/s', 'n_gpus': world, 'steps': K, 'warmup': W,
-            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
-            'data': 'synthetic',
-            'config': {'workload': '%s, %d lockstep envs per MI355X, %s, 5 simulation steps per env step, %d PGS sweeps' % (env_id, n, 'random-policy rollout' if workload is None else ('scripted press-and-wipe policy on the device (tool force feedback), whole 200-step episodes from starts with the pad on the arm; the pad carries force in %.0f %% of the selection rollout' % (100 * dense_touching)) if workload == 'dense' else 'pad pressed onto the arm at every reset, 8-step episodes, small random actions (x%.2f)' % action_scale, int(blob.param('NITER'))),
-                       'envs_per_gpu': n, 'global_envs': world * n, 'reset_pool': pool, 'reset': args.reset, 'parallelism': 'env-sharded x%d' % world,
-                       'obs_allgather': bool(distributed), 'gather': gather_how, 'gathered_record': 'obs | reward | done | total_force_on_human | task_success' if distributed else None,
-                       'gathered_in_global_order': in_order, 'noop_retest': blob.param('NOOP_RETEST'),
-                       **({'ranks_share_gpus': '%d ranks on %d device(s): a rehearsal of the N-rank command (--share-gpus), not a scaling point' % (world, torch.cuda.device_count())} if getattr(args, 'share_gpus', False) else {})},
+        out.update({
             'contacts_per_substep': contacts,      # solver contacts of the last substep of a step, mean over environments and sampled steps
             'overflow_count': int(overflow),       # substeps (summed over environments) in which a contact was dropped by the contact / row / coefficient budgets
-            'pool_states_refreshed': int(getattr(env, 'pool_refreshed', 0)),      # --pool-refresh: start states a child process sampled during the run and the rollout swapped into the pool
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
                          'traffic': traffic, 'traffic_source': traffic_src,
                          'kernel': names[dom], 'kernel_ms_per_launch': launch_ms, 'launches_per_step': launches[dom],
@@ -575,7 +612,7 @@ def run_config(args, task, steps, warmup, rank, world, local_rank, distributed, 
                          'stream_ms_per_step': kernel_ms / K,
                          'step_level_achieved': bytes_per_env_step * n / (elapsed / K) / 1e9,
                          'note': 'solver bound by the latency of the dependent chain through the rows that share a body (wide row-local sweep: 1.38 rows per 38-instruction step, 56 % of the wave cycles at s_waitcnt: DESIGN 5), not by HBM; HBM fraction reported as the contract requires (SURVEY 8d)'},
-        }
+        })
         if cloth_kernel:
             out['roofline']['cloth_kernel'] = cloth_kernel
         if world == 1 and cpu:
@@ -598,12 +635,15 @@ def main():
     ap.add_argument('--reset', choices=['pool', 'device', 'host'], default='pool',
                     help="'pool': auto-reset from a fixed device-generated pool (BASELINE config 2); 'device': new states sampled for every episode")
     ap.add_argument('--pool-refresh', type=int, default=0, help='k > 0: a child process samples k new start states at a time and the rollout swaps them into the pool at episode boundaries (vec_env.PoolRefresher); the line then reports pool_states_refreshed')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='beside the headline: the CPU-oracle baseline, per-kernel / roofline figures, contact and overflow counts, '
+                    'the other BASELINE configurations and the exact-solver / 2,000-step companions of the headline (a plain run times the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step returned (obs, reward, done, info) to DIR/<name>.npy, float32')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: without the CPU-oracle baseline')
     ap.add_argument('--task', choices=sorted(TASKS), default=None, help="'feeding' = the BASELINE metric (config 2, the default); 'bedbathing' = config 3; 'scratchitch' = config 4's env (co-op) on one GPU; 'dressing' = config 5's")
     ap.add_argument('--workload', choices=['wiping', 'dense'], default=None, help="bedbathing only: 'wiping' = pad pressed onto the arm at every reset, 8-step episodes, small random actions; 'dense' = whole 200-step episodes under a scripted press-and-wipe policy (BASELINE config 3: dense tool-skin contact)")
     ap.add_argument('--env', default=None, help="any built env id instead of --task, e.g. 'ScratchItchJaco-v1' or 'FeedingSawyerHuman-v1' (assistive_gym_amd.envs.ENV_IDS)")
     ap.add_argument('--param', action='append', default=[], help='override a PARAMS entry of the model blob, e.g. --param NOOP_RETEST=0 (same-box A/B runs)')
-    ap.add_argument('--no-configs', action='store_true', help='the default 1-GPU run also times short runs of BASELINE configs 3, 4 (1 GPU), 5 (1 GPU) into "configs"; this skips them')
+    ap.add_argument('--no-configs', action='store_true', help='--full also times short runs of BASELINE configs 3, 4 (1 GPU), 5 (1 GPU) into "configs"; this skips them')
     ap.add_argument('--backend', default=None, help="torch.distributed backend (default nccl = RCCL; gloo with --dry-run)")
     ap.add_argument('--force-gather', action='store_true', help='1 GPU: run the multi-GPU code path anyway (a 1-rank RCCL process group, the per-step observation all-gather on its side stream) -- what the stream / hardware-queue layout of --gpus N looks like on one GPU')
     ap.add_argument('--gather', choices=['abi', 'torch'], default='abi', help="the collective of the per-step whole-batch gather with --gpus N: 'abi' = agx_comm_init_rank / agx_allgather of the C ABI (RCCL bound by libagx), 'torch' = torch.distributed")
@@ -624,9 +664,9 @@ def main():
         if world > 1:
             dist.init_process_group(args.backend or 'gloo')
         out = dry_run(args, rank, world)
-        if args.task is None and args.env is None and world in MULTI_GPU_CONFIGS and not args.no_configs:
+        if args.full and args.task is None and args.env is None and world in MULTI_GPU_CONFIGS and not args.no_configs:
             key, t, _ = MULTI_GPU_CONFIGS[world]
-            r = dry_run(argparse.Namespace(**dict(vars(args), task=t)), rank, world)
+            r = dry_run(argparse.Namespace(**dict(vars(args), task=t, dump_outputs=None)), rank, world)
             out.setdefault('configs', {})[key] = dict({k: r[k] for k in ('value', 'unit', 'n_gpus', 'steps', 'ms_per_step')}, workload=r['config']['workload'], global_envs=r['config']['global_envs'],
                                                        gather=r['config']['gather'], gathered_in_global_order=r['config']['gathered_in_global_order'])
         if rank == 0:
@@ -659,8 +699,10 @@ def main():
             dist.init_process_group(args.backend)
     headline = args.task is None and args.env is None
     task = args.task or 'feeding'
-    out = run_config(args, task, args.steps, args.warmup, rank, world, local_rank, distributed, cpu=not args.no_cpu_baseline, workload=args.workload, env_id_override=args.env)
-    if headline and world == 1 and not args.no_configs:
+    out = run_config(args, task, args.steps, args.warmup, rank, world, local_rank, distributed, cpu=not args.no_cpu_baseline, workload=args.workload, env_id_override=args.env,
+                     dump=args.dump_outputs)
+    configs = args.full and headline and not args.no_configs
+    if configs and world == 1:
         # beside the headline: the same workload over 2,000 steps (ten episode boundaries inside the window) when the timed
         # window was short, and with the EXACT solver -- NOOP_RETEST = 0: every row visited in every sweep, no re-test rule -- over 300 steps
         if args.steps < 200:
@@ -670,7 +712,7 @@ def main():
         r = run_config(args0, task, 300, 20, rank, world, local_rank, distributed, cpu=False)
         out['value_noop_retest_0'] = r['value']
         out['value_noop_retest_0_note'] = 'same process, 300 steps, --param NOOP_RETEST=0: plain projected Gauss-Seidel, every row visited in all %d sweeps' % int(r['config']['workload'].split(',')[-1].split()[0])
-    if headline and world in MULTI_GPU_CONFIGS and not args.no_configs:
+    if configs and world in MULTI_GPU_CONFIGS:
         # the driver's 4- and 8-rank commands also run BASELINE config 4 (ScratchItchPR2 co-op, 16,384 environments over 4 GPUs) / config 5
         # (DressingBaxter, 32,768 over 8) as written: same sharding, same per-step whole-batch gather (every rank takes part: collectives)
         key, t, st = MULTI_GPU_CONFIGS[world]
@@ -679,7 +721,7 @@ def main():
             out.setdefault('configs', {})[key] = dict({k: r[k] for k in ('value', 'unit', 'n_gpus', 'steps', 'ms_per_step', 'contacts_per_substep', 'overflow_count')},
                                                        workload=r['config']['workload'], global_envs=r['config']['global_envs'], gather=r['config']['gather'],
                                                        gathered_in_global_order=r['config']['gathered_in_global_order'])
-    if headline and world == 1 and not args.no_configs:
+    if configs and world == 1:
         # the other single-GPU BASELINE configurations on the same clock: short runs (a few seconds each), the headline value above is config 2
         extra = {}
         for key, t, wl, st in (('config3_BedBathingSawyer-v1', 'bedbathing', None, 300), ('config3_BedBathingSawyer-v1_wiping_contact', 'bedbathing', 'wiping', 300),

@@ -228,12 +228,11 @@ def _remap(a):
 
 
 def test_h5_reader_and_blob_weights(bed):
-    """assets/realistic_arm_limits_model.h5 read without h5py: 8,705 parameters, tanh x3 + sigmoid; the blob carries them"""
+    """assets/realistic_arm_limits_model.h5 of the reference (a copy: tests/golden/) read without h5py: 8,705 parameters, tanh x3 + sigmoid
+    (SURVEY appendix D); the blob carries them"""
     import os
     from assistive_gym_amd.model.h5lite import H5File, load_keras_dense_stack
-    path = '/root/reference/assistive_gym/envs/assets/realistic_arm_limits_model.h5'
-    if not os.path.exists(path):
-        pytest.skip('reference assets not on this box')
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'realistic_arm_limits_model.h5')
     ds = H5File(path).datasets()
     assert ds['/model_weights/dense_1/dense_1/kernel:0'].shape == (4, 64) and ds['/optimizer_weights/Adam/iterations:0'] == 425200
     stack = load_keras_dense_stack(path)

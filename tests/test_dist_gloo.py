@@ -176,16 +176,17 @@ def test_bench_gpus_flag_spawns_its_own_ranks():
 
 @pytest.mark.parametrize('world', [2, 4, 8])
 def test_driver_n_rank_command_line_fields(world):
-    """The driver's N-rank command (`bench.py --gpus N --steps K --warmup W`, no --task, default 4096 environments per GPU) on the dry-run
-    path: the one JSON line carries n_gpus = N, global_envs = N x 4096, how the gather was done and that the whole batch arrived in global
-    env order; the 4- and 8-rank commands ALSO run BASELINE config 4 (ScratchItchPR2 co-op, 16,384 environments over 4 GPUs) / config 5
-    (DressingBaxter, 32,768 over 8) under "configs" (VERDICT r5 next 8)."""
+    """The driver's N-rank command with --full (`bench.py --gpus N --steps K --warmup W --full`, no --task, default 4096 environments per
+    GPU) on the dry-run path: the one JSON line carries n_gpus = N, global_envs = N x 4096, how the gather was done and that the whole batch
+    arrived in global env order; the 4- and 8-rank commands ALSO run BASELINE config 4 (ScratchItchPR2 co-op, 16,384 environments over 4
+    GPUs) / config 5 (DressingBaxter, 32,768 over 8) under "configs" (VERDICT r5 next 8).  A plain run (no --full) leaves them out:
+    test_plain_n_rank_command_dumps_the_gathered_batch."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--dry-run', '--backend', 'gloo', '--steps', '3', '--warmup', '1'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--dry-run', '--backend', 'gloo', '--steps', '3', '--warmup', '1', '--full'],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -200,6 +201,33 @@ def test_driver_n_rank_command_line_fields(world):
     else:
         e = j['configs'][want[0]]
         assert e['n_gpus'] == world and e['global_envs'] == want[1] and want[2] in e['workload'] and e['gathered_in_global_order'] and e['gather']
+
+
+def test_plain_n_rank_command_dumps_the_gathered_batch(tmp_path):
+    """the plain N-rank command (no --full) times the headline alone -- no "configs", even at 4 ranks -- and --dump-outputs writes rank 0's
+    outputs of the last timed step and the gathered whole-batch record, in global env order"""
+    import json
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    world, n, K, W = 4, 8, 3, 1
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--dry-run', '--backend', 'gloo', '--steps', str(K), '--warmup', str(W),
+                        '--envs-per-gpu', str(n), '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    j = json.loads(lines[0])
+    assert j['n_gpus'] == world and j['steps'] == K and j['config']['global_envs'] == world * n and j['config']['gathered_in_global_order']
+    assert 'configs' not in j
+    full = np.load(str(tmp_path / 'gathered_record.npy'))
+    obs = np.load(str(tmp_path / 'obs.npy'))
+    assert full.dtype == np.float32 and full.shape == (world * n, 25 + 4) and obs.shape == (n, 25)
+    assert np.array_equal(full[:, 24], np.arange(world * n)) and np.array_equal(full[:n, :25], obs)        # rank 0's rows first, global env index in the last column
+    g = torch.Generator(); g.manual_seed(1001)                                                              # rank 0's action tape (bench.dry_run)
+    tape = (torch.rand((W + K, n, 7), generator=g) * 2 - 1).numpy()
+    assert np.array_equal(obs[:, :7], tape[W + K - 1]) and not np.array_equal(obs[:, :7], tape[W + K - 2])   # the LAST timed step's actions
 
 
 def test_real_bench_path_votes_on_the_collective_and_checks_the_order():

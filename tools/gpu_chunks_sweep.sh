@@ -6,7 +6,7 @@ O=$R/gpurun_out/${1:-r03m}
 rm -rf $O && mkdir -p $O
 cd $R
 for c in 1 2 3 4 5 6 8; do
-  AGX_CHUNKS=$c timeout 200 python bench.py --task ${2:-feeding} --steps 300 --warmup 20 --no-cpu-baseline --no-configs > $O/chunks$c.json 2> $O/chunks$c.err
+  AGX_CHUNKS=$c timeout 200 python bench.py --task ${2:-feeding} --steps 300 --warmup 20 --full --no-cpu-baseline --no-configs > $O/chunks$c.json 2> $O/chunks$c.err
   python - <<PY
 import json
 try:

@@ -8,7 +8,7 @@ rm -rf $O && mkdir -p $O
 cd $R
 (timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -15) > $O/gputest.log; tail -3 $O/gputest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python - <<PY
 import json
 try:
@@ -16,8 +16,8 @@ try:
 except Exception as e: print('default failed', e)
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_feeding -- python $R/bench.py --task feeding --steps 50 --warmup 5 --no-cpu-baseline --no-configs > $O/bench_under_rocprof_feeding.json 2> $O/s1.err
-AGX_CHUNKS=1 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_unchunked_feeding -- python $R/bench.py --task feeding --steps 50 --warmup 5 --no-cpu-baseline --no-configs > $O/bench_unchunked_under_rocprof_feeding.json 2> $O/s2.err
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_feeding -- python $R/bench.py --task feeding --steps 50 --warmup 5 --full --no-cpu-baseline --no-configs > $O/bench_under_rocprof_feeding.json 2> $O/s1.err
+AGX_CHUNKS=1 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_unchunked_feeding -- python $R/bench.py --task feeding --steps 50 --warmup 5 --full --no-cpu-baseline --no-configs > $O/bench_unchunked_under_rocprof_feeding.json 2> $O/s2.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pmc_workload_dressing -- python $R/tools/pmc_workload.py dressing > /dev/null 2> $O/s3.err
 if [ -n "${AGX_FINAL_NO_PMC:-}" ]; then echo "(PMC passes skipped: AGX_FINAL_NO_PMC)"; else
 for c in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do

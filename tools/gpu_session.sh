@@ -8,8 +8,8 @@
 #   file:<path>      pytest -m gpu <path>
 #   smoke            __graft_entry__.smoke()
 #   driver           the driver's exact command: bench.py --gpus 1 --steps 20 --warmup 5 -> driver_cmd.json
-#   default          bench.py with every config -> bench_default_all_configs.json
-#   bench:<args>     bench.py <args> (commas for spaces) --no-cpu-baseline --no-configs -> bench_<args>.json
+#   default          bench.py --full: every config -> bench_default_all_configs.json
+#   bench:<args>     bench.py <args> (commas for spaces) --full --no-cpu-baseline --no-configs -> bench_<args>.json
 #   prof / prof1     rocprofv3 --kernel-trace --stats of bench.py --steps 50 (prof1: AGX_CHUNKS=1) -> kernel_stats_[unchunked_]feeding.csv
 #   prof:<task>      the same for --task <task>
 #   pmc:<task>       the separate --pmc passes over tools/pmc_workload.py <task>, reduced by tools/pmc_traffic.py -> traffic_<task>.json
@@ -17,7 +17,7 @@
 #   py:<script>[,args]  python <script> args -> <script basename>.log
 #   env:VAR=VAL / unset:VAR   environment for the actions that follow (e.g. env:AGX_SOLVE_LDS_BYTES=12288)
 #   bits:<name>      tools/gpu_lv_bits.py: 40 steps of 1,024 FeedingJaco environments, default build against lib/variants/<name>.so, bit by bit -> bits_<name>.txt
-#   share[:N]        the driver's N-rank command (default 2) with all ranks on this box's one GPU: bench.py --gpus N --backend gloo --share-gpus -> share_gpus_N.json
+#   share[:N]        the driver's N-rank command (default 2) with all ranks on this box's one GPU: bench.py --gpus N --full --backend gloo --share-gpus -> share_gpus_N.json
 #   bitsenv:<name>,<VecEnv class>[,<class> ...]   the same for other tasks' environments (512 x 30 steps) -> bitsenv_<name>.txt
 #   ab:<name>        AGX_LIB=assistive_gym_amd/lib/variants/<name>.so bench.py --steps 300 (x2, interleaved with the default build) -> ab_<name>.txt
 set -u
@@ -43,11 +43,11 @@ for A in "$@"; do
     file) N=$(basename "$V" .py); timeout 1800 python -m pytest "$V" -m gpu -q -rs -x > $O/pytest_$N.log 2>&1; echo "rc=$?"; grep -E "^FAILED|^ERROR|passed|failed|Error" $O/pytest_$N.log | tail -12 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -1 $O/smoke.log ;;
     driver) timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd.json 2>$O/driver_cmd.err; line $O/driver_cmd.json ;;
-    default) timeout 1200 python bench.py > $O/bench_default_all_configs.json 2>$O/bench_default.err; line $O/bench_default_all_configs.json ;;
-    bench) N=$(echo "$V" | tr -c 'A-Za-z0-9=' '_')${AGX_SOLVE_LDS_BYTES:+_lds$AGX_SOLVE_LDS_BYTES}; timeout 900 python bench.py $(echo "$V" | tr ',' ' ') --no-cpu-baseline --no-configs > $O/bench_$N.json 2>$O/bench_$N.err; line $O/bench_$N.json ;;
+    default) timeout 1200 python bench.py --full > $O/bench_default_all_configs.json 2>$O/bench_default.err; line $O/bench_default_all_configs.json ;;
+    bench) N=$(echo "$V" | tr -c 'A-Za-z0-9=' '_')${AGX_SOLVE_LDS_BYTES:+_lds$AGX_SOLVE_LDS_BYTES}; timeout 900 python bench.py $(echo "$V" | tr ',' ' ') --full --no-cpu-baseline --no-configs > $O/bench_$N.json 2>$O/bench_$N.err; line $O/bench_$N.json ;;
     prof|prof1) T=${V:-feeding}; S=""; [ $K = prof1 ] && S="unchunked_"
       if [ $K = prof1 ]; then export AGX_CHUNKS=1; fi
-      ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_tmp -- python $R/bench.py --task $T --steps 50 --warmup 5 --no-cpu-baseline --no-configs > $O/bench_${S}under_rocprof_$T.json 2>$O/rocprof_$T.err )
+      ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_tmp -- python $R/bench.py --task $T --steps 50 --warmup 5 --full --no-cpu-baseline --no-configs > $O/bench_${S}under_rocprof_$T.json 2>$O/rocprof_$T.err )
       [ $K = prof1 ] && unset AGX_CHUNKS
       find $O/prof_tmp -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/kernel_stats_${S}$T.csv; head -6 $O/kernel_stats_${S}$T.csv; rm -rf $O/prof_tmp ;;
     pmc) T=${V:-feeding}; mkdir -p $O/pmc
@@ -61,7 +61,7 @@ for A in "$@"; do
     ab) : > $O/ab_$V.txt
       for rep in 1 2; do for L in default $V; do
         if [ $L = default ]; then unset AGX_LIB; else export AGX_LIB=$R/assistive_gym_amd/lib/variants/$V.so; fi
-        timeout 300 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-configs 2>/dev/null | python -c "
+        timeout 300 python bench.py --steps 300 --warmup 30 --full --no-cpu-baseline --no-configs 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', round(j['value']), round(j['ms_per_step'], 3), {k.split('_')[1]: round(v, 2) for k, v in j['roofline']['kernels_ms_per_step_summed_over_overlapping_launches'].items()})" | tee -a $O/ab_$V.txt
       done; done; unset AGX_LIB ;;
@@ -70,7 +70,7 @@ j = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', round(j['
         echo "$E: $(python tools/gpu_lv_bits.py --compare /tmp/be_default.npz /tmp/be_$L.npz | tail -1)" | tee -a $O/bitsenv_$L.txt; done ;;
     bits) timeout 600 python tools/gpu_lv_bits.py /tmp/bits_default.npz 1024 40 > /dev/null 2>$O/bits_$V.err; AGX_LIB=$R/assistive_gym_amd/lib/variants/$V.so timeout 600 python tools/gpu_lv_bits.py /tmp/bits_$V.npz 1024 40 > /dev/null 2>>$O/bits_$V.err
       python tools/gpu_lv_bits.py --compare /tmp/bits_default.npz /tmp/bits_$V.npz | tail -2 | tee $O/bits_$V.txt ;;
-    share) N=${V:-2}; timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --steps 50 --warmup 5 --backend gloo --share-gpus --no-cpu-baseline > $O/share_gpus_$N.json 2>$O/share_gpus_$N.err; echo "rc=$?"; line $O/share_gpus_$N.json; tail -3 $O/share_gpus_$N.err ;;
+    share) N=${V:-2}; timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --steps 50 --warmup 5 --full --backend gloo --share-gpus --no-cpu-baseline > $O/share_gpus_$N.json 2>$O/share_gpus_$N.err; echo "rc=$?"; line $O/share_gpus_$N.json; tail -3 $O/share_gpus_$N.err ;;
     env) export "$V"; echo "exported $V" ;;
     unset) unset "$V" ;;
     *) echo "unknown action $A" ;;
