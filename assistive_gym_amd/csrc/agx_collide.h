@@ -197,14 +197,8 @@ AGX_DEV float rel_travel(const Ctx& c, int a, int b) {
   const v3 u = (va - vb) + cross(dw, ce - ld3(c.lds + L_MISC + M_REF));
   const float rot = (sa || sb) ? 0.f : sqrtf(dot(dw, dw)) * 0.5f * sqrtf(dot(d, d));
   const float t = 1.001f * (sqrtf(dot(u, u)) + rot) * c.dt + 1e-6f;
-  if constexpr (ABS == 7) return fminf(t, AB[ABS * a + 6] + AB[ABS * b + 6]);       // (the old layout: never above the sum of the absolute travels)
-  else return t;
+  return fminf(t, AB[ABS * a + 6] + AB[ABS * b + 6]);             // never above the sum of the absolute travels
 }
-#ifdef AGX_SWEEP_TWO_SIDED
-#define AGX_SWEEP_ONE_SIDED_COND false
-#else
-#define AGX_SWEEP_ONE_SIDED_COND (CLI(c, a, AGX_C_NVERT) == 1)
-#endif
 // conservative separation test: every point of collider x lies within |half extents| + radius of
 // the centre of its box; collider y lies within its body-frame box inflated by its radius.  True if
 // the two are certainly further apart than `reach`.
@@ -248,11 +242,7 @@ AGX_DEV void collide_flush(Ctx& c, int wn, CollideState& cs, float brk, float sl
     }
     k.n = mk3(0.f, 0.f, 0.f); k.pa = k.n; k.pb = k.n; k.dist = 0.f;
     bool hit = narrowphase(c, a, b, lim, k, has && sub == 0);
-#ifdef AGX_NARROWPHASE_TWICE   // timing experiment: the narrowphase of every pass a second time (same result) -- the slowdown of the step is what ONE
-    { Cand k2; k2.gap = 3.0e38f; k2.n = mk3(0.f, 0.f, 0.f); k2.pa = k2.n; k2.pb = k2.n; k2.dist = 0.f;     // narrowphase costs under the chunk overlap,
-      const bool h2 = narrowphase(c, a, b, lim + 1e-9f, k2, has && sub == 0);                               // i.e. the ceiling of any gain there
-      if (h2 && k2.dist == 12345.678f) k.gap = 0.f; }
-#endif
+    // (timed with every narrowphase run twice, round 4: 473 -> 427 k env-steps/s, the ceiling of any gain here; profiles/r04/r04u_ab_feeding_narrowphase_twice.txt)
     // on a face GJK's closest point is an arbitrary point of the face: the first contact of a pair resting on a static
     // world box is re-anchored at a vertex as well (oracle: face_manifold)
     if (has && sub == 0 && hit && k.n.z > 0.999f && face_box(c, b) && CLI(c, a, AGX_C_NVERT) >= 2) { Cand k0; k0.gap = k.gap; if (face_point(c, a, b, 0, k.pa, k0)) k = k0; }
@@ -382,8 +372,9 @@ AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gfl
     if (ok) for (int q = 0; q < 3; q++) if (AB[ABS * a + q] > AB[ABS * b + 3 + q] + mg || AB[ABS * b + q] > AB[ABS * a + 3 + q] + mg) ok = false;
     // level 3: bounding sphere of one collider against the body-frame box of the other, both ways
     // (the second test -- b's bounding sphere against a's body-frame box -- cannot reject what the first one passed when a is a sphere: its
-    // box is the point itself, so the test degenerates to two bounding spheres; skipped then: AGX_SWEEP_ONE_SIDED)
-    if (ok) { const float reach = mg + rel_travel(c, a, b) + 1e-5f; ok = !sphere_box_apart(c, a, b, reach) && (AGX_SWEEP_ONE_SIDED_COND || !sphere_box_apart(c, b, a, reach)); }
+    // box is the point itself, so the test degenerates to two bounding spheres; skipped then.  Both tests always: 468 k either way, round 4;
+    // profiles/r04/r04q_ab_feeding_one_sided_sphere_cull.txt)
+    if (ok) { const float reach = mg + rel_travel(c, a, b) + 1e-5f; ok = !sphere_box_apart(c, a, b, reach) && (CLI(c, a, AGX_C_NVERT) == 1 || !sphere_box_apart(c, b, a, reach)); }
     const uint64_t m = wave_ballot(ok);
     const int slot = wn + wave_rank(m);
     if (ok && slot < WL_CAP) WL[slot] = a | (b << 9) | (g << 18) | (sub << 24);
@@ -427,7 +418,7 @@ AGX_DEV void collide(Ctx& c) {
       float h = fabsf(R.a[3 * k]) * hl.x + fabsf(R.a[3 * k + 1]) * hl.y + fabsf(R.a[3 * k + 2]) * hl.z + r;
       AB[ABS * col + k] = comp(cw, k) - h - grow; AB[ABS * col + 3 + k] = comp(cw, k) + h + grow;
     }
-    if constexpr (ABS == 7) AB[ABS * col + 6] = grow;
+    AB[ABS * col + 6] = grow;
   }
   wave_sync();
   AGX_CTICK(8)

@@ -31,7 +31,7 @@ constexpr int MAX_ROWS = 160;
 #endif
 constexpr int ST_WORDS = AGX_ST_WORDS;
 constexpr int CON_STRIDE = 16;
-// row headers of the scratch record.  Variants whose solve kernel has the row-local sweep (agx_pgs_lv.h: LV_COMPILED -- the same condition) keep TWO
+// row headers of the scratch record.  Variants whose solve kernel has the row-local sweeps (agx_pgs_lvs.h: LV_COMPILED -- the same condition) keep TWO
 // tables: 32 bytes per row with exactly what a visit of that sweep needs (one 8-word scalar load, agx_pgs_lvs.h; two rows per cache line), and
 // behind it 8 words per row for the register sweep (DoF lane masks, mu).  The others keep the one 10-word table of rounds 1-4.
 constexpr bool HDR_WIDE = AGX_MAX_DOF <= 16 && AGX_MAX_BLOCK <= 10 && AGX_TASK == AGX_TASK_FEEDING;
@@ -41,16 +41,9 @@ constexpr int HDR_STRIDE = HDR_WIDE ? 8 : 10;                              // wo
 #endif
 constexpr int ARENA_WORDS = AGX_ARENA_WORDS;
 constexpr int MAX_QPT = 16;                              // manifold points of the (wiping pad, human) pairs handed to the finish kernel
-// collider table stride: world AABB (6) + the collider's own travel distance (1).  -DAGX_AABB_WITHOUT_TRAVEL (A/B knob): without the seventh word
-// -- rel_travel() (agx_collide.h) then bounds the narrowphase limit alone -- the worklist gets 256 words of the arena back: 200 entries instead
-// of 182, one flush instead of two for a FeedingJaco substep (23 instead of 28 passes per step on the emulator, bit-identical contacts).  Measured
-// on the last GPU seconds of round 4 (profiles/r04/r04v_ab_feeding_worklist_200.txt): 469.5 / 468.2 k against 468.8 k -- no difference, so the
-// layout the GPU suite ran on stays the default.
-#if defined(AGX_AABB_WITHOUT_TRAVEL) && !defined(AGX_NO_REL_TRAVEL)
-constexpr int ABS = 6;
-#else
+// collider table stride: world AABB (6) + the collider's own travel distance (1).  Without the seventh word (round 4: the worklist gets 200
+// entries instead of 182, bit-identical contacts) 469.5 / 468.2 k against 468.8 k -- no difference; profiles/r04/r04v_ab_feeding_worklist_200.txt.
 constexpr int ABS = 7;
-#endif
 
 // ---- LDS layout (float words) -------------------------------------------------------------
 constexpr int L_ST = 0;
@@ -78,7 +71,7 @@ constexpr int LDS_BYTES = LDS_WORDS * 4;
 // rows beyond the window stream from the global scratch (L2)
 constexpr int L_SOLVE_ENT = L_VEL + 128;
 // Build-time knobs for same-box A/B runs (tools/ab_build.sh): -DAGX_SOLVE_LDS_PAIRS=n (size of the solve kernel's
-// LDS row window), -DAGX_NO_LDS_ROWS (all rows from global memory), -DAGX_PGS_CPP (the C++ twin of the assembly sweep).
+// LDS row window), -DAGX_PGS_CPP (the C++ twin of the assembly sweep).
 #ifndef AGX_SOLVE_LDS_PAIRS
 #define AGX_SOLVE_LDS_PAIRS 960
 #endif

@@ -34,33 +34,19 @@ AGX_DEV v3 gjk_vertex0(const gjk_shape& s) {
 // Same comparisons in the same order, and `R v + p` still works on a fresh 12-byte load: BIT-IDENTICAL with 0 on 13 task / robot combinations
 // (512-1,024 environments x 30-40 steps each, profiles/r06/r06w_*), 615.2 / 615.7 k against 610.6 / 610.5 k env-steps/s, same box, interleaved.
 // (Sixteen per round: bit-identical too, 66 instead of 62 spilled registers, 609.7 / 610.0 k against 616.5 / 615.3 k -- eight it is.)
-// 1 (an A/B knob): the winner's coordinates carried along instead of re-loaded -- one round trip less, 614-621 k -- but the winner then sits in three
-// separate registers, and `R v + p`, which the compiler rounds differently at every inlined call site (packed products, partly fused chains), comes out with
-// other last bits whatever sequence is pinned (gjk_xf).  Two pinned sequences were run through the GPU suite: 203 of 205 tests passed each time, and each
-// time two OTHER tests on ill-conditioned states (a threshold contact of a crafted pressed state; the co-op arm one step after a classifier roll-back; a
-// wiping force) missed margins the suite's own rounding meets.  Not worth re-basing those margins (profiles/r06/r06u_ab_gjk_scan_wide.txt).
+// (The winner's coordinates carried along instead of re-loaded, formerly value 1: one round trip less, 614-621 k, but `R v + p` on three separate
+// registers comes out with other last bits whatever rounding sequence is pinned, and 2 of 205 GPU tests on ill-conditioned states missed their
+// margins with each of two sequences; profiles/r06/r06u_ab_gjk_scan_wide.txt.)
 #ifndef AGX_GJK_SCAN_WIDE
 #define AGX_GJK_SCAN_WIDE 2
+#endif
+#if AGX_GJK_SCAN_WIDE != 0 && AGX_GJK_SCAN_WIDE != 2
+#error "AGX_GJK_SCAN_WIDE: 0 or 2"
 #endif
 #ifndef AGX_GJK_SCAN_ONE
 #define AGX_GJK_SCAN_ONE 1
 #endif
 
-// R v + p of the scan's winner with ONE rounding sequence, p + fma(R2, z, fma(R1, y, [R0 x])), written with a product and a sum the compiler may not
-// contract or re-associate.  (Left to the compiler, `mul(R, v) + p` came out differently at every inlined call site -- packed products, partly fused
-// chains, another pattern for the third component -- so the support points of A and of B were rounded by different rules, and neither like the CPU wave
-// emulator.  With the wide scan the winner sits in three separate registers and the patterns would have shifted once more: pinned instead.)
-#ifdef __HIPCC__
-AGX_DEV float gjk_nc_mul(float a, float b) { return __fmul_rn(a, b); }
-AGX_DEV float gjk_nc_add(float a, float b) { return __fadd_rn(a, b); }
-#else
-AGX_DEV float gjk_nc_mul(float a, float b) { volatile float r = a * b; return r; }
-AGX_DEV float gjk_nc_add(float a, float b) { volatile float r = a + b; return r; }
-#endif
-AGX_DEV float gjk_xf1(float r0, float r1, float r2, float x, float y, float z, float p) { return gjk_nc_add(p, fmaf(r2, z, fmaf(r1, y, gjk_nc_mul(r0, x)))); }
-AGX_DEV v3 gjk_xf(const m3& R, v3 p, float x, float y, float z) {
-  return mk3(gjk_xf1(R.a[0], R.a[1], R.a[2], x, y, z, p.x), gjk_xf1(R.a[3], R.a[4], R.a[5], x, y, z, p.y), gjk_xf1(R.a[6], R.a[7], R.a[8], x, y, z, p.z));
-}
 AGX_DEV v3 gjk_support(const gjk_shape& s, v3 d) {
   if (s.box) {
     // vertex order of the 8-corner enumeration (x major): first maximum wins, like the vertex scan
@@ -78,13 +64,10 @@ AGX_DEV v3 gjk_support(const gjk_shape& s, v3 d) {
   const float* V = s.v;
 #if AGX_GJK_SCAN_WIDE
   const int last = s.n - 1;
-  float bd = -3.0e38f, bx = 0.f, by = 0.f, bz = 0.f; int best = 0;
+  float bd = -3.0e38f; int best = 0;
 #define GJK_LDV(j, kk) const int i##j = (kk) < last ? (kk) : last; const float x##j = V[3 * i##j], y##j = V[3 * i##j + 1], z##j = V[3 * i##j + 2];
-#if AGX_GJK_SCAN_WIDE == 2     // the winner by INDEX, loaded again at the end (one round trip more): `R v + p` keeps the operands -- a fresh 12-byte load -- it has in the 4-per-round scan
+// the winner by INDEX, loaded again at the end (one round trip more): `R v + p` keeps the operands -- a fresh 12-byte load -- it has in the 4-per-round scan
 #define GJK_CMP(j) { const float t = gjk_dot3(x##j, y##j, z##j, dl); if (t > bd) { bd = t; best = i##j; } }
-#else
-#define GJK_CMP(j) { const float t = gjk_dot3(x##j, y##j, z##j, dl); if (t > bd) { bd = t; bx = x##j; by = y##j; bz = z##j; } }
-#endif
   int k = 0;
 #if AGX_GJK_SCAN_ONE
   if (s.n > 1)       // a one-vertex core (a food particle, a bead of the tool) has nothing to scan: its support point is one round trip, not two
@@ -101,13 +84,7 @@ AGX_DEV v3 gjk_support(const gjk_shape& s, v3 d) {
   }
 #undef GJK_LDV
 #undef GJK_CMP
-#if AGX_GJK_SCAN_WIDE == 2
-  (void)bx; (void)by; (void)bz;
   return mul(s.R, mk3(V[3 * best], V[3 * best + 1], V[3 * best + 2])) + s.p;
-#else
-  (void)best;
-  return gjk_xf(s.R, s.p, bx, by, bz);
-#endif
 #else
   int best = 0;
   float bd = gjk_dot3(V[0], V[1], V[2], dl);
@@ -134,11 +111,8 @@ AGX_DEV v3 gjk_support(const gjk_shape& s, v3 d) {
 // (Tried at the end of round 6: two served lanes per turn and the winners loaded by their own lanes in one load behind the loop -- 618.0 / 618.4 k against
 // 616.8 / 616.6 k, and NOT bit-identical: `R v + p` moved out of the loop is rounded by another pattern.  The served scans are coalesced loads; they are
 // not where a pass waits.  Dropped: profiles/r06/r06z_ab_coop_scan_batched.txt.)
-#ifdef AGX_GJK_NO_COOP   // build-time knob for A/B runs: every lane scans its own hull
-constexpr int GJK_COOP_MIN = 32, GJK_COOP_MAX_LANES = 0;
-#else
+// (Round 1, with the GJK early-out, against every lane scanning its own hull: 379.6 -> 395.5 k env-steps/s; CHANGELOG.md 5.1.)
 constexpr int GJK_COOP_MIN = 32, GJK_COOP_MAX_LANES = 16;
-#endif
 AGX_DEV v3 gjk_support_wave(const gjk_shape& s, v3 d, bool active) {
   const bool big = active && !s.box && s.n > GJK_COOP_MIN;
   uint64_t hm = wave_ballot(big);

@@ -114,30 +114,16 @@ static_assert(AGX_SOLVE_ENT_BYTES == 4 * L_SOLVE_ENT, "LDS offset of the row win
   "1:\n" \
   LOAD(Z1, "v88") \
   "2:\n"
-// The address arithmetic of the row-ahead fetch, woven into the wait states of the reduction.  -DAGX_PGS_NO_ADDR (timing ablation, results
-// meaningless: the fetch reads the zero pair): solve kernel 1.51 -> 1.11 ms per 4096 FeedingJaco environments -- these 3 v_readlane and
-// 4 vector instructions cost 26 %.  Tried instead (round 2, correct on the GPU, slower): per-row fetch headers read with scalar loads and
+// The address arithmetic of the row-ahead fetch, woven into the wait states of the reduction.  Timed without it (round 2, results meaningless:
+// the fetch read the zero pair; CHANGELOG.md, tools/micro_solve.py): solve kernel 1.51 -> 1.11 ms per 4096 FeedingJaco environments -- these
+// 3 v_readlane and 4 vector instructions cost 26 %.  Tried instead (round 2, correct on the GPU, slower): per-row fetch headers read with scalar loads and
 // the pairs of a row's two contiguous DoF ranges loaded under EXEC = the range's lanes (2 vector instructions per row instead of 11, but
 // 4 global loads per row and no LDS window): 2.7 ms -- a wave64 load costs the memory pipe the same whatever its EXEC mask.
-#ifdef AGX_PGS_NO_ADDR
-#define AGX_PGS_ADDR0 "s_mov_b32 s84, 0\n"
-#define AGX_PGS_ADDR1 ""
-#define AGX_PGS_ADDR2 ""
-#define AGX_PGS_ADDR3 "v_mov_b32_e32 v85, 0\n"
-#define AGX_PGS_ADDR4 "s_bitcmp1_b32 s84, 31\n"
-#elif defined(AGX_PGS_NO_READLANE3)   // timing ablation (results meaningless): the three v_readlane of the row-ahead fetch as scalar moves -- what fetching the row descriptors some other way (scalar loads) could save at most
-#define AGX_PGS_ADDR0 "s_mov_b32 s84, 8\n" "s_mov_b32 s82, 0xfff\n"
-#define AGX_PGS_ADDR1 "s_mov_b32 s83, 0\n" "s_bitcmp1_b32 s84, 31\n"
-#define AGX_PGS_ADDR2 "v_mbcnt_lo_u32_b32 v81, s82, 0\n"
-#define AGX_PGS_ADDR3 "v_mbcnt_hi_u32_b32 v81, s83, v81\n" "v_add_lshl_u32 v85, v81, s84, 3\n"
-#define AGX_PGS_ADDR4 "v_cndmask_b32_e64 v85, 0, v85, s[82:83]\n"
-#else
 #define AGX_PGS_ADDR0 "v_readlane_b32 s84, %[off], s80\n" "v_readlane_b32 s82, %[mlo], s80\n"
 #define AGX_PGS_ADDR1 "v_readlane_b32 s83, %[mhi], s80\n" "s_bitcmp1_b32 s84, 31\n"
 #define AGX_PGS_ADDR2 "v_mbcnt_lo_u32_b32 v81, s82, 0\n"
 #define AGX_PGS_ADDR3 "v_mbcnt_hi_u32_b32 v81, s83, v81\n" "v_add_lshl_u32 v85, v81, s84, 3\n"
 #define AGX_PGS_ADDR4 "v_cndmask_b32_e64 v85, 0, v85, s[82:83]\n"
-#endif
 #define AGX_PGS_DPP(CTRL) "v_add_f32_dpp v80, v80, v80 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
 // One row: the dependent chain (dot product, 6-step DPP reduction, impulse update, broadcast) with the
 // address arithmetic of the prefetch for row r+3 woven into its wait states.
@@ -265,12 +251,10 @@ AGX_DEV void pgs_load_set(const Ctx& c, int row, bool ok, bool friction, PgsSet&
   S.pack = ok ? Xi[H_PACK] : 0; S.off = ok ? Hi[H_OFF] : 0;
   S.mlo = ok ? Xi[H_MLO] : 0; S.mhi = ok ? Xi[H_MHI] : 0; S.m2 = ok ? Xi[H_M2] : 0;
 }
-// first lane of [l0, l1) whose row reaches beyond the LDS window of (J,B) pairs (l1 if none)
+// first lane of [l0, l1) whose row reaches beyond the LDS window of (J,B) pairs (l1 if none).  (Every row from global memory: 449 against 453 k
+// env-steps/s, round 5; profiles/r05/r05d_ab_no_lds_window.txt.)
 AGX_DEV int pgs_lds_split(const PgsSet& S, int lane, int l0, int l1) {
   if (l1 <= l0) return l0;
-#ifdef AGX_NO_LDS_ROWS
-  return l0;
-#endif
   const int end = (S.off & 0x7fffffff) + ((S.pack >> 8) & 255) + (int)((unsigned)S.pack >> 24);
   const uint64_t m = wave_ballot(lane >= l0 && lane < l1 && end > SOLVE_LDS_PAIRS);
   return wave_uniform(m ? ffs64(m) : l1);

@@ -1,8 +1,15 @@
-// agx_pgs_lvs.h -- K6, the row-local sweep with nothing but velocities and pairs in LDS (AGX_PGS_LV == 3, the default of the feeding variant).
-// Part of the stepper (see agx_step.h); included by agx_step.h only, after agx_pgs_lv.h (whose visit it restates on a leaner layout).
+// agx_pgs_lvs.h -- K6, the row-local sweep (AGX_PGS_LV == 3): velocity deltas and pairs in LDS, lane = ENTRY of the visited row, one row per
+// visit.  With AGX_PGS_LV == 4, the default of the feeding variant, it is compiled in as the fallback and bit-identity partner of the wide sweep
+// of agx_pgs_lvw.h (AGX_P_SOLVE_WIDE = 0, rows the scheduler cannot place).  Part of the stepper (see agx_step.h); included by agx_step.h only.
+// This file also holds what the two row-local sweeps share: AGX_PGS_LV, LV_G, LV_COMPILED, lv_eligible and the LDS / global accessors.
 //
-// agx_pgs_lv.h keeps an 8-word header per row and a 16-bit velocity slot per pair in LDS beside the pairs: 17.6 KB for an ordinary FeedingJaco
-// substep (1,350 pairs, 123 rows), i.e. 8 solve waves per CU.  Here a visit gets
+// Why (round 5).  The register sweep of agx_pgs.h keeps the velocity deltas in registers (lane = DoF) and pays for that layout at every row
+// visit: the (J,B) pairs of a row are found by the rank of the lane inside the row's DoF mask, the dot product is a 6-step reduction over 64
+// lanes and a v_readlane, the impulse change travels back through another -- 25 vector instructions per visit, five of them cross-lane
+// (profiles/r03/solve_kernels_sq_counters.md).  build_rows() stores the pairs of a row CONTIGUOUSLY, and a row of the feeding scenes has at
+// most 16 of them (10 robot DoFs + 6 of a free body).  So lane k < 16 holds entry k of the visited row: it gathers dv[slot_k] from LDS, the dot
+// product is a 4-step xor butterfly inside ONE 16-lane DPP row whose result is bitwise the same in the 16 lanes (wave_sum16), every lane
+// evaluates the impulse update, and scatters dv[slot_k] += B_k dlambda.  A visit here gets
 //   * the row's header -- 1/D, b, lo, hi, pair offset, pair counts, velocity slot offsets: the 32-byte row of the first header table build_rows()
 //     leaves in the scratch record -- through the SCALAR cache: one s_load_dwordx8 three visits ahead, the values are used straight from
 //     scalar registers;
@@ -11,27 +18,60 @@
 //   * the velocity slot of a pair by arithmetic on one header word;
 //   * its pairs from the LDS window, or -- the rows beyond it: the tail of the friction rows, most of which the no-op rule skips -- from the
 //     scratch record (global_load, vmcnt).
-// LDS holds the velocity deltas (128 words) and the window: 10 KB per solve wave (16 per CU), three LDS instructions per visit instead of
-// seven.  Same rows, same order, same clamps, same arithmetic as pgs_lv(): the two are BIT-IDENTICAL on the GPU (tests/test_gpu_solve_variants.py,
-// tools/gpu_lv_bits.py, profiles/r05/r05i_bits_*) and in the emulator, whatever the window.
+// LDS holds the velocity deltas (128 words) and the window: 10 KB per solve wave (16 per CU), three LDS instructions per visit.  Same rows,
+// same order, same clamps, same no-op re-test rule and friction skipping as pgs(); the sums are associated differently (rounding only).
+// AGX_P_WARMSTART > 0 and rows longer than 16 entries keep the register sweep (lv_eligible).
 //
-// MEASURED (round 5, same box, 4096 FeedingJaco environments, 300 steps; profiles/r05/r05h..r05s).  env-steps/s: pgs_lv() at 20 KB 522 k;
-// this file at 9.5 / 10 / 11 / 12 KB of LDS 561 / 566 / 555 / 547 k (with the headers as 64-byte rows of one table: 544 / 552 / 546 / 540 k --
-// the 32-byte table halves the lines a sweep pulls through the scalar cache and lets the live headers of an XCD fit its L2: HBM-side
-// traffic of a solve launch 70 -> 31 KB per environment).  Shader cycles per row and sweep with one / sixteen waves per CU: 159 / 213 at
-// 10 KB (64-byte rows: 159 / 266; pgs_lv: 155 / 168 with eight).  What did NOT help: impulses and friction bounds in LDS arrays instead of the register
-// (three fewer vector instructions, three more LDS instructions: 521 k; tools/experiments/agx_pgs_lvs_impulses_in_lds.h); the write-back of
-// the impulse and the loop test moved into the shadow of the next gather (546 k).  What did: the scalar instructions of the header request
-// in the wait states the DPP butterfly needs anyway (538 -> 552 k, measured on the 64-byte rows like the probes below); rows beyond the
-// window waiting for their OWN pair only (vmcnt 1): 566 -> 569 k, and the 9.5 KB launch as fast as the 10 KB one.  Warming the scalar cache
-// with the next part's first header lines at the start of a part: no difference (568 / 569 k, r05u_*).
-// Marginal cost of ONE more instruction per visit, measured with redundant instructions (AGX_LVS_PROBE_*, r05m_*), one / sixteen waves
-// per CU: vector 5.9 / 3.8 cycles, scalar 5.5 / 5.9, s_nop 5.5 / 4.2, LDS read 21 / 6, LDS write 11 / 9 -- of a visit of 268 / 448 cycles and
-// 38 instructions.  A wave pays 4..6 cycles for every instruction it issues, of whatever kind, in both regimes: the sweep is bound by the
-// per-wave issue rate of a dependent chain, not by a pipe; what is left is the instruction count per visit.
+// MEASURED (round 5, same box, 4096 FeedingJaco environments, 300 steps; profiles/r05/).  Register sweep 467 k env-steps/s.  The first
+// row-local sweep kept an 8-word header per row and a 16-bit velocity slot per pair in LDS as well (agx_pgs_lv.h, AGX_PGS_LV = 1 / 2, retired;
+// last in commit 1d72094): as hipcc compiled its C++ loop ~110 instructions per visit, 430 k; its visit in gfx950 assembly (45 instructions,
+// 155 / 168 shader cycles per row and sweep with one / eight waves per CU) 522 k at 20 KB of LDS, 437 k at 9.5 KB.  This file at 9.5 / 10 /
+// 11 / 12 KB 561 / 566 / 555 / 547 k (r05h..r05s; 159 / 213 cycles with one / sixteen waves at 10 KB; with the headers as 64-byte rows of
+// one table: 544 / 552 / 546 / 540 k -- the 32-byte table halves the lines a sweep pulls through the scalar cache and lets the live headers of
+// an XCD fit its L2: HBM-side traffic of a solve launch 70 -> 31 KB per environment).  What did NOT help: impulses and friction bounds in LDS
+// arrays instead of the register (521 k; tools/experiments/README.md); the write-back of the impulse and the loop test moved into the shadow of
+// the next gather (546 k).  What did: the scalar instructions of the header request in the wait states the DPP butterfly needs anyway
+// (538 -> 552 k, on the 64-byte rows); rows beyond the window waiting for their OWN pair only (vmcnt 1): 566 -> 569 k, and the 9.5 KB
+// launch as fast as the 10 KB one.  Warming the scalar cache with the next part's first header lines: no difference (r05u_*).
+// Marginal cost of ONE more instruction per visit, measured with redundant instructions (r05m_*), one / sixteen waves per CU: vector 5.9 /
+// 3.8 cycles, scalar 5.5 / 5.9, s_nop 5.5 / 4.2, LDS read 21 / 6, LDS write 11 / 9 -- of a visit of 268 / 448 cycles and 38 instructions.
+// A wave pays 4..6 cycles for every instruction it issues, of whatever kind, in both regimes: the sweep is bound by the per-wave issue rate
+// of a dependent chain, not by a pipe; what is left is the instruction count per visit.
 #pragma once
 
 namespace agx {
+
+// AGX_PGS_LV: 4 (default) the wide sweep of agx_pgs_lvw.h with this one as its fallback; 3 this sweep alone; 0 the register sweep of agx_pgs.h
+#ifndef AGX_PGS_LV
+#define AGX_PGS_LV 4
+#endif
+static_assert(AGX_PGS_LV == 0 || AGX_PGS_LV == 3 || AGX_PGS_LV == 4, "AGX_PGS_LV: 0, 3 or 4 (1 and 2, the LDS-header sweep, are retired)");
+constexpr int LV_G = 16;                                            // lanes of a visit = the longest row this path takes
+constexpr bool LV_COMPILED = AGX_PGS_LV && HDR_WIDE;       // the `feeding` variant (Jaco, Panda); rows of at most 16 pairs are checked per environment (lv_eligible)
+
+// LDS accessors of the hot loops.  On the device they take ABSOLUTE LDS byte addresses (32 bit, what a ds_read wants in its address register).
+// Explicit address spaces (a flat access would count against vmcnt AND lgkmcnt).  On the emulator an "address" is a byte offset from the LDS array.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef float lv_v2 __attribute__((ext_vector_type(2)));
+#define LV_LDS(T) __attribute__((address_space(3))) T*
+#define LV_GLB(T) const __attribute__((address_space(1))) T*
+AGX_DEV int lv_addr(const float* lds, const void* p) { (void)lds; return (int)(uintptr_t)(LV_LDS(const char))(const char*)p; }
+AGX_DEV void lv_ld2(const float* lds, int a, float& x, float& y) { (void)lds; const lv_v2 v = *(LV_LDS(const lv_v2))(uintptr_t)a; x = v.x; y = v.y; }
+AGX_DEV float lv_ld1(const float* lds, int a) { (void)lds; return *(LV_LDS(const float))(uintptr_t)a; }
+AGX_DEV void lv_st1(float* lds, int a, float v) { (void)lds; *(LV_LDS(float))(uintptr_t)a = v; }
+AGX_DEV void lv_ld2g(const float* p, float& x, float& y) { const lv_v2 v = *(LV_GLB(lv_v2))p; x = v.x; y = v.y; }
+#else
+AGX_DEV int lv_addr(const float* lds, const void* p) { return (int)((const char*)p - (const char*)lds); }
+AGX_DEV void lv_ld2(const float* lds, int a, float& x, float& y) { const float* p = (const float*)((const char*)lds + a); x = p[0]; y = p[1]; }
+AGX_DEV float lv_ld1(const float* lds, int a) { return *(const float*)((const char*)lds + a); }
+AGX_DEV void lv_st1(float* lds, int a, float v) { *(float*)((char*)lds + a) = v; }
+AGX_DEV void lv_ld2g(const float* p, float& x, float& y) { x = p[0]; y = p[1]; }
+#endif
+
+// may this environment take a row-local sweep?  (wave uniform)
+AGX_DEV bool lv_eligible(const Ctx& c) {
+  return c.ndof <= LV_G && c.nrobot + 6 <= LV_G && c.nhdof + 6 <= LV_G && c.nv <= 128 && !(PRM(c, AGX_P_WARMSTART) > 0.f) && c.nrows > 0;
+}
 
 constexpr bool LVS_COMPILED = (AGX_PGS_LV == 3 || AGX_PGS_LV == 4) && LV_COMPILED;      // (4: the wide sweep of agx_pgs_lvw.h, with this one as its fallback)
 constexpr int LVS_SOLVE_LDS_BYTES = 10240;                          // LDS of a solve launch of that variant: 16 waves per CU; the window (1,216 pairs) holds the non-contact and normal rows of an ordinary substep and most friction rows
@@ -64,7 +104,7 @@ struct LvsLay { float* lds; const float* H; const float* E; int dv_addr, pairs_a
 
 #if !defined(__HIP_DEVICE_COMPILE__) || defined(AGX_PGS_LV_CPP)
 // One visit, the C++ statement of what the assembly loop does: what the emulator runs (tests/test_emu_parity.py holds it bit-identical with
-// pgs_lv()'s twin).  -DAGX_PGS_LV_CPP compiles it for the device as well (a debugging aid, never run on hardware).
+// the wide sweep's twin, lvw_step).  -DAGX_PGS_LV_CPP compiles it for the device as well (a debugging aid, never run on hardware).
 // lam: this lane's impulse register (lane = row - base); hiv: friction parts, mu x the normal impulse of the lane's contact (else unused).
 AGX_DEV void lvs_visit(const LvsLay& Y, int lane, int base, int bit, float& lam, bool fric, bool far, float hiv) {
   const float* H = Y.H + HDR_STRIDE * (base + bit); const int* Hi = (const int*)H;
@@ -95,29 +135,7 @@ AGX_DEV void lvs_visit(const LvsLay& Y, int lane, int base, int bit, float& lam,
 // s[52:83] headers, s84..s87 their bit indices, s[88:89] cursor, s[90:93] on-masks, s94..s97 impulses / friction bounds,
 // s98 visits left, s99 scratch, vcc; v88..v93 entries (pair, slot address), v94..v99 temporaries.
 #define LVS_DPP(CTRL) "v_add_f32_dpp v95, v95, v95 " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
-// AGX_LVS_PROBE_*: marginal cost of one more instruction of a kind inside a visit -- redundant instructions that change no result
-// (tools/gpu_r05_s13.sh; profiles/r05/r05m_*): n extra instructions per visit
-#define LVS_REP0(x)
-#define LVS_REP1(x) x
-#define LVS_REP2(x) x x
-#define LVS_REP4(x) x x x x
-#define LVS_REPN(n, x) LVS_REPN_(n, x)
-#define LVS_REPN_(n, x) LVS_REP##n(x)
-#ifndef AGX_LVS_PROBE_VALU
-#define AGX_LVS_PROBE_VALU 0
-#endif
-#ifndef AGX_LVS_PROBE_SALU
-#define AGX_LVS_PROBE_SALU 0
-#endif
-#ifndef AGX_LVS_PROBE_NOP
-#define AGX_LVS_PROBE_NOP 0
-#endif
-#ifndef AGX_LVS_PROBE_LDSR
-#define AGX_LVS_PROBE_LDSR 0
-#endif
-#ifndef AGX_LVS_PROBE_LDSW
-#define AGX_LVS_PROBE_LDSW 0
-#endif
+// (round 5 timed redundant instructions of each kind inside a visit here: the marginal costs in the header above, profiles/r05/r05m_*)
 #define LVS_YES(x) x
 #define LVS_NO(x)
 #define LVS_NOT_LVS_YES(x)
@@ -145,9 +163,7 @@ AGX_DEV void lvs_visit(const LvsLay& Y, int lane, int base, int bit, float& lam,
 #define LVS_STEP(FRIC, FAR, C_INVD, C_B, C_LO, C_HI, C_BIT, N1_OFF, N1_N, N1_NA, N1_AB, N1_BIT, N3_OCT, N3_BIT, EC_J, EC_B, EC_IA, EC_ON, EC_LAM, EC_HI, EN_JB, EN_IA, EN_ON, EN_ONLO, EN_LAM, EN_HI) \
   "ds_read_b32 v94, " EC_IA "\n" \
   LVS_ENTRY(FRIC, FAR, N1_OFF, N1_N, N1_NA, N1_AB, N1_BIT, EN_JB, EN_IA, EN_ON, EN_ONLO, EN_LAM, EN_HI) \
-  LVS_REPN(AGX_LVS_PROBE_LDSR, "ds_read_b32 v97, " EC_IA "\n") \
   LVS_WAIT(FAR) \
-  LVS_REPN(AGX_LVS_PROBE_VALU, "v_mov_b32_e32 v97, 0\n") LVS_REPN(AGX_LVS_PROBE_SALU, "s_mov_b32 s99, 0\n") LVS_REPN(AGX_LVS_PROBE_NOP, "s_nop 0\n") \
   "v_mul_f32_e32 v95, " EC_J ", v94\n" \
   "v_cndmask_b32_e64 v95, 0, v95, " EC_ON "\n" \
   /* the header request of visit t + 3 and two moves fill the wait states a DPP read of a fresh register needs (2 each) */ \
@@ -170,7 +186,6 @@ AGX_DEV void lvs_visit(const LvsLay& Y, int lane, int base, int bit, float& lam,
   "v_fmac_f32_e32 v94, " EC_B ", v97\n" \
   "s_mov_b64 exec, " EC_ON "\n" \
   "ds_write_b32 " EC_IA ", v94\n" \
-  LVS_REPN(AGX_LVS_PROBE_LDSW, "ds_write_b32 " EC_IA ", v94\n") \
   "v_readfirstlane_b32 s99, v96\n" \
   "s_lshl_b64 exec, 1, " C_BIT "\n" \
   "v_mov_b32_e32 %[lam], s99\n" \

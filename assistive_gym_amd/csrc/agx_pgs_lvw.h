@@ -21,7 +21,7 @@
 //   * the row's header from the two compact tables build_rows() leaves in the scratch record (agx_ctx.h: Q -- 1/D, b, lo, hi, a lane reads
 //     word k & 3 and takes the others from its quad through DPP operand selects; P -- pair offset, pair counts, velocity slot offsets, packed
 //     so that SDWA byte / word selects pick the fields without unpacking), requested three steps ahead;
-//   * its pair from the LDS window (or, a step with a row beyond it, every lane from the scratch record), its velocity slot from LDS, the
+//   * its pair from the LDS window (or, a row beyond it, from the scratch record), its velocity slot from LDS, the
 //     4-step butterfly inside the DPP row, the impulse update in all 16 lanes alike, the scatter; impulses live in LDS (one word per row: the
 //     16 lanes of a group store the same value to the same address, no EXEC juggling).
 // 36 instructions per step (the narrow sweep: 38 per row).  LDS: velocity deltas, impulses, three step lists, the window -- 10 KB per wave.
@@ -164,19 +164,9 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
   "s_cbranch_vccnz " LBL "1f\n" \
   "ds_read_b64 " JB ", v124\n" \
   LBL "2:\n"
-// (AGX_LVW_FAR_ALL_LANES=1: the first version -- every lane of a far step took its pair from the scratch record, 64 loads of which two thirds fetched pairs the
-// window holds, or nothing a row owns (k >= n).  Now: the lanes of rows inside the window read LDS as in a near step -- the LDS count of the step is the same --
-// and only the on-lanes of the rows beyond it load from the record.  Same values either way.)
-#ifndef AGX_LVW_FAR_ALL_LANES
-#define AGX_LVW_FAR_ALL_LANES 0
-#endif
-#if AGX_LVW_FAR_ALL_LANES
-#define LVW_FAR(LBL, P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) \
-  LBL "1:\n" \
-  "v_add_u32_sdwa v124, " P0 ", %[k8] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD\n" \
-  "global_load_dwordx2 " JB ", v124, %[E]\n" \
-  "s_branch " LBL "2b\n"
-#else
+// A far step: the lanes of rows inside the window read LDS as in a near step -- the LDS count of the step is the same -- and only the on-lanes of
+// the rows beyond it load from the scratch record.  (The first version loaded every lane of a far step from the record, 64 loads of which two thirds
+// fetched pairs the window holds or nothing a row owns: same bits, same speed, twice the solve kernel's HBM traffic; profiles/r06/r06m_ab_far_path_per_lane.txt.)
 #define LVW_FAR(LBL, P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) \
   LBL "1:\n" \
   "s_andn2_b64 exec, exec, vcc\n" \
@@ -186,15 +176,11 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
   "global_load_dwordx2 " JB ", v124, %[E]\n" \
   "s_mov_b64 exec, -1\n" \
   "s_branch " LBL "2b\n"
-#endif
 #define LVW_GATHER(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "ds_read_b32 v123, " IA "\n"
-// The end of a step.  Default (AGX_LVW_EARLY_GATHER, round 6): the scatter, then the GATHER OF THE NEXT STEP -- it only has to follow the scatter (LDS executes a
-// wave's accesses in order) -- and only then the impulse store; the loop counter is decremented in a wait state of the butterfly (nothing between there and the
-// branch touches SCC).  -DAGX_LVW_EARLY_GATHER=0: the first version (impulse store, scatter, counter, branch; the gather opens the next step).
-#ifndef AGX_LVW_EARLY_GATHER
-#define AGX_LVW_EARLY_GATHER 1
-#endif
-#if AGX_LVW_EARLY_GATHER
+// The end of a step: the scatter, then the GATHER OF THE NEXT STEP -- it only has to follow the scatter (LDS executes a wave's accesses in order) --
+// and only then the impulse store; the loop counter is decremented in a wait state of the butterfly (nothing between there and the branch touches
+// SCC).  (The first version -- impulse store, scatter, counter, branch; the gather opened the next step -- 607 k against 610 k env-steps/s, round 6;
+// profiles/r06/r06g_ab_early_gather.txt.)
 #define LVW_END(LA, SON, IA, GNEXT, SUBEND) \
   "s_mov_b64 exec, " SON "\n" \
   "ds_write_b32 " IA ", v123\n" \
@@ -203,23 +189,8 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
   "ds_write_b32 " LA ", v122\n" \
   SUBEND \
   "s_cbranch_scc1 9f\n"
-#define LVW_TOP_GATHER(...)
-#define LVW_PRIME_GATHER(...) LVS_APPLY(LVW_GATHER, __VA_ARGS__)
 #define LVW_TAIL_STEP "s_sub_u32 s60, s60, 1\n"
 #define LVW_SUBEND_STEP
-#else
-#define LVW_END(LA, SON, IA, GNEXT, SUBEND) \
-  "ds_write_b32 " LA ", v122\n" \
-  "s_mov_b64 exec, " SON "\n" \
-  "ds_write_b32 " IA ", v123\n" \
-  "s_mov_b64 exec, -1\n" \
-  "s_sub_u32 s60, s60, 1\n" \
-  "s_cbranch_scc1 9f\n"
-#define LVW_TOP_GATHER(...) LVS_APPLY(LVW_GATHER, __VA_ARGS__)
-#define LVW_PRIME_GATHER(...)
-#define LVW_TAIL_STEP "s_nop 0\n"
-#define LVW_SUBEND_STEP
-#endif
 #define LVW_SUBEND_LAST "s_sub_u32 s60, s60, 1\n"
 // S4 with the S2 of step t + 3 and the S1 of step t + 4 in the wait states the butterfly needs (two between a write and a DPP read of it)
 #define LVW_S4(FRIC, S2TEXT_A, S2TEXT_B, S2TEXT_C, S1TEXT, S1B, TAIL, GNEXT, SUBEND, P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) \
@@ -250,16 +221,10 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
 #define LVW_RID(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) RID
 // one step: C the slot of step t, N1 of t + 1, N3 of t + 3 (S1 of t + 4 re-uses C's row index register: its step has long passed S2)
 #define LVW_ITER(FRIC, LBL, OFF, TAIL, SUBEND, C, N1, N3) \
-  LVW_TOP_GATHER(C) \
   "s_waitcnt vmcnt(2)\n" \
   LVS_APPLY(LVW_S3, FRIC, LBL, N1) \
   "s_waitcnt lgkmcnt(1)\n" \
-  LVS_APPLY(LVW_S4, FRIC, LVS_APPLY(LVW_S2_A, N3), LVS_APPLY(LVW_S2_B, N3), LVS_APPLY(LVW_S2_C, N3), LVW_S1(LVS_APPLY(LVW_RID, C), OFF), LVW_S1B(LVS_APPLY(LVW_RID, C)), TAIL, LVW_GNEXT(N1), SUBEND, C)
-#if AGX_LVW_EARLY_GATHER
-#define LVW_GNEXT(...) LVS_APPLY(LVW_GATHER, __VA_ARGS__)
-#else
-#define LVW_GNEXT(...)
-#endif
+  LVS_APPLY(LVW_S4, FRIC, LVS_APPLY(LVW_S2_A, N3), LVS_APPLY(LVW_S2_B, N3), LVS_APPLY(LVW_S2_C, N3), LVW_S1(LVS_APPLY(LVW_RID, C), OFF), LVW_S1B(LVS_APPLY(LVW_RID, C)), TAIL, LVS_APPLY(LVW_GATHER, N1), SUBEND, C)
 #define LVW_BODY(FRIC) \
     "s_mov_b64 s[50:51], exec\n" \
     "s_mov_b64 exec, -1\n" \
@@ -269,7 +234,7 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
     LVS_APPLY(LVW_S2, LVW_SL0) LVS_APPLY(LVW_S2, LVW_SL1) \
     "s_waitcnt vmcnt(2)\n" \
     LVS_APPLY(LVW_S3, FRIC, "7", LVW_SL0) \
-    LVW_PRIME_GATHER(LVW_SL0) \
+    LVS_APPLY(LVW_GATHER, LVW_SL0) \
     LVS_APPLY(LVW_S2, LVW_SL2) \
     "8:\n" \
     LVW_ITER(FRIC, "1", "16", LVW_TAIL_STEP, LVW_SUBEND_STEP, LVW_SL0, LVW_SL1, LVW_SL3) \

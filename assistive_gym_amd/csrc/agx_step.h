@@ -18,7 +18,7 @@
 //
 // Files: agx_ctx.h (limits, LDS / scratch layouts, per-lane context), agx_dyn.h (kinematics, ABA, M^-1),
 // agx_collide.h (broadphase, GJK narrowphase, contact selection), agx_rows.h (constraint rows),
-// agx_pgs.h (Gauss-Seidel sweeps, gfx950 assembly), agx_env.h (integration, task layer, kernel bodies),
+// agx_pgs.h / agx_pgs_lvs.h / agx_pgs_lvw.h (Gauss-Seidel sweeps, gfx950 assembly), agx_env.h (integration, task layer, kernel bodies),
 // agx_reset.h (device-side reset generator: sampling + IK restarts, float64).
 #pragma once
 #include "agx_math.h"
@@ -29,7 +29,6 @@
 #include "agx_collide.h"
 #include "agx_rows.h"
 #include "agx_pgs.h"
-#include "agx_pgs_lv.h"
 #include "agx_pgs_lvs.h"
 #include "agx_pgs_lvw.h"
 #if AGX_TASK == 5   /* AGX_TASK_DRINKING (an enum: not visible to the preprocessor) */

@@ -12,13 +12,9 @@
 #define AGX_WAVE 64
 
 AGX_DEV int wave_lane() { return (int)(threadIdx.x & 63u); }
-#ifdef AGX_WAVE_SYNC_LDS_ONLY   // timing experiment only (NOT safe: some sync points order global scratch traffic between lanes): how much of the
-                                // kernels' time is the workgroup fence of __syncthreads() waiting for outstanding global loads / stores?
-                                // Measured (same box, profiles/r04/r04t_ab_feeding_lds_only_wave_sync.txt): none -- 473.3 vs 473.2 k env-steps/s.
-AGX_DEV void wave_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#else
+// (How much of the kernels' time is this fence waiting for outstanding global loads / stores?  None: an LDS-only wait, 473.3 vs 473.2 k
+// env-steps/s; profiles/r04/r04t_ab_feeding_lds_only_wave_sync.txt.)
 AGX_DEV void wave_sync() { __syncthreads(); }
-#endif
 // orders this wavefront's own LDS accesses in the compiler; the hardware executes a wavefront's LDS instructions in order, so no wait
 AGX_DEV void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
@@ -68,7 +64,7 @@ AGX_DEV int wave_sum_i(int x) {
   return __builtin_amdgcn_readlane(x, 63);
 }
 // sum over the 16 lanes of this lane's DPP row as an xor butterfly (1, 2, half mirror, mirror): every lane adds the same two numbers at
-// every step, so the result is bitwise the same in all 16 lanes -- no broadcast afterwards (the row-local sweep, agx_pgs_lv.h)
+// every step, so the result is bitwise the same in all 16 lanes -- no broadcast afterwards (the row-local sweeps, agx_pgs_lvs.h / agx_pgs_lvw.h)
 #define AGX_DPP_ROW_HALF_MIRROR 0x141
 #define AGX_DPP_ROW_MIRROR 0x140
 AGX_DEV float wave_sum16(float x) {

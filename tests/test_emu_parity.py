@@ -605,14 +605,14 @@ def test_all_solver_switches_together_match_the_oracle(blob):
     o.forget_warm()
 
 
-def test_row_local_sweep_against_the_register_sweep(blob):
-    """The row-local sweep (csrc/agx_pgs_lv.h, -DAGX_PGS_LV=2: velocity deltas in LDS, lane = entry of the visited row -- on the device its
-    visit loop is the assembly twin of the C++ run here) against the register sweep (csrc/agx_pgs.h, built with -DAGX_PGS_LV=0) and against itself with a 300-pair LDS window
+def test_wide_row_local_sweep_against_the_register_sweep(blob):
+    """The row-local sweep of the default build (csrc/agx_pgs_lvw.h: velocity deltas in LDS, lane = entry of the visited row -- on the device its
+    step loop is the assembly twin of the C++ run here) against the register sweep (csrc/agx_pgs.h, built with -DAGX_PGS_LV=0) and against itself with a 300-pair LDS window
     (most rows stream their pairs from the scratch record): same rows, same order, same clamps -- the dot products are associated
     differently, so the three agree to rounding, not bit for bit, and the window size must not change a bit."""
     from emu_lib import Emu
     from oracle_lib import Oracle
-    lv, reg, cap, oracle = Emu(blob, 'feeding_lv2'), Emu(blob, 'feeding_reg'), Emu(blob, 'feeding_lv_cap'), Oracle(blob)
+    wide, reg, cap, oracle = Emu(blob), Emu(blob, 'feeding_reg'), Emu(blob, 'feeding_lvw_cap'), Oracle(blob)
     st, _ = make_states(blob, 2, seed=3701)
     rng = np.random.RandomState(8)
     differs = 0
@@ -622,7 +622,7 @@ def test_row_local_sweep_against_the_register_sweep(blob):
         for k in range(2):
             a = rng.uniform(-1, 1, blob.act_dim).astype(np.float32)
             s_l, s_r, s_c, s_o = s.copy(), s.copy(), s.copy(), s.copy()
-            l_obs, l_rew, _, l_info, _ = lv.step(s_l, a)
+            l_obs, l_rew, _, l_info, _ = wide.step(s_l, a)
             r_obs, r_rew, _, r_info, _ = reg.step(s_r, a)
             c_obs, c_rew, _, c_info, _ = cap.step(s_c, a)
             o_obs, o_rew, _, o_info = oracle.step(s_o, a)
@@ -638,16 +638,13 @@ def test_row_local_sweep_against_the_register_sweep(blob):
     assert differs > 0                                     # (two different sweeps: a real comparison)
 
 
-def test_wide_row_local_sweep_is_bit_identical(blob):
-    """csrc/agx_pgs_lvw.h (the default solve path of the feeding variant since round 6: up to four rows with disjoint velocity slots per visit, one per
-    16-lane group, list-scheduled per substep) against csrc/agx_pgs_lvs.h (one row per visit, the default of round 5): rows that share no slot
-    commute exactly and rows that do keep their order, so states, observations, rewards and info agree BIT FOR BIT -- over settling (the bowl
-    lands, food falls onto the spoon) and steps; also with a 300-pair LDS window (steps with a row beyond it read every pair from the scratch
-    record), with the blob switch AGX_P_SOLVE_WIDE = 0 (the narrow sweep inside the wide build), and in a build whose scheduler gives up at 8
-    steps per part (the fallback to the narrow sweep, substep by substep)."""
+def _wide_sweep_against_the_narrow_builds(blob, dirs):
+    """The five builds of test_wide_row_local_sweep_is_bit_identical, BIT FOR BIT; `dirs` friction rows per contact.  The debug record of the
+    first substep of every step shows that the wide sweep ran there (words DBG_TIME + 16..19: steps, rows visited, scheduled steps, rows)."""
     from emu_lib import Emu
     wide, narrow, cap, few = Emu(blob), Emu(blob, 'feeding_lvs'), Emu(blob, 'feeding_lvw_cap'), Emu(blob, 'feeding_lvw_8steps')
     off = Emu(blob.set_param('SOLVE_WIDE', 0))
+    T = wide.DBG_TIME
     st, _ = make_states(blob, 3, seed=3703)
     rng = np.random.RandomState(10)
     for i in range(3):
@@ -662,20 +659,40 @@ def test_wide_row_local_sweep_is_bit_identical(blob):
             outs = []
             for e in (wide, narrow, cap, few, off):
                 se = s.copy()
-                obs, rew, done, info, _ = e.step(se, a)
+                obs, rew, done, info, dbg = e.step(se, a, debug=e is wide)
                 outs.append((se, obs, rew, info))
+                if e is wide:                              # contacts with `dirs` friction rows each, and the wide sweep solved them
+                    ncon, nrows, nnc = int(dbg[0]), int(dbg[1]), int(dbg[3])
+                    assert ncon > 0 and nrows == nnc + (1 + dirs) * ncon, (i, k, ncon, nrows, nnc)
+                    assert dbg[T + 16] > 0 and dbg[T + 17] > 0 and dbg[T + 18] > 0 and dbg[T + 19] == nrows, (i, k, dbg[T + 16:T + 20])
             for name, (se, obs, rew, info) in zip(('narrow', 'window of 300 pairs', 'scheduler limited to 8 steps', 'SOLVE_WIDE = 0'), outs[1:]):
                 assert np.array_equal(se.view(np.uint32), outs[0][0].view(np.uint32)) and np.array_equal(obs, outs[0][1]) and rew == outs[0][2] and np.array_equal(info, outs[0][3]), (i, k, name)
             s = outs[0][0]
 
 
-def test_row_local_sweep_with_scalar_headers(blob):
+def test_wide_row_local_sweep_is_bit_identical(blob):
+    """csrc/agx_pgs_lvw.h (the default solve path of the feeding variant since round 6: up to four rows with disjoint velocity slots per visit, one per
+    16-lane group, list-scheduled per substep) against csrc/agx_pgs_lvs.h (one row per visit, the default of round 5): rows that share no slot
+    commute exactly and rows that do keep their order, so states, observations, rewards and info agree BIT FOR BIT -- over settling (the bowl
+    lands, food falls onto the spoon) and steps; also with a 300-pair LDS window (steps with a row beyond it read every pair from the scratch
+    record), with the blob switch AGX_P_SOLVE_WIDE = 0 (the narrow sweep inside the wide build), and in a build whose scheduler gives up at 8
+    steps per part (the fallback to the narrow sweep, substep by substep)."""
+    _wide_sweep_against_the_narrow_builds(blob, 1)
+
+
+def test_wide_row_local_sweep_is_bit_identical_with_two_friction_directions(blob):
+    """The same five builds with AGX_P_FRICTION_DIRS = 2 (a second friction row per contact): the wide sweep schedules the friction rows once and
+    visits the second direction's rows on the same steps (csrc/agx_pgs_lvw.h pgs_lvw), which only this blob switch reaches."""
+    _wide_sweep_against_the_narrow_builds(blob.set_param('FRICTION_DIRS', 2.0), 2)
+
+
+def test_narrow_row_local_sweep_against_the_wide_sweep(blob):
     """csrc/agx_pgs_lvs.h (the fallback of the wide sweep; the default of round 5: row headers through scalar loads from the scratch record, impulses in a vector register, velocity
-    slots by arithmetic on the header) does the arithmetic of csrc/agx_pgs_lv.h visit by visit: the two agree BIT FOR BIT, and so does a build whose LDS
-    window holds 300 pairs only (most rows read their pairs from the scratch record: the window is a cache, not arithmetic); the register sweep
+    slots by arithmetic on the header) does the arithmetic of the default build's wide sweep (csrc/agx_pgs_lvw.h) row by row: the two agree BIT FOR BIT, and so does a build
+    whose LDS window holds 300 pairs only (most rows read their pairs from the scratch record: the window is a cache, not arithmetic); the register sweep
     (-DAGX_PGS_LV=0) associates the dot products differently and agrees to rounding."""
     from emu_lib import Emu
-    lv, lvs, cap, reg = Emu(blob, 'feeding_lv2'), Emu(blob, 'feeding_lvs'), Emu(blob, 'feeding_lvs_cap'), Emu(blob, 'feeding_reg')
+    wide, lvs, cap, reg = Emu(blob), Emu(blob, 'feeding_lvs'), Emu(blob, 'feeding_lvs_cap'), Emu(blob, 'feeding_reg')
     st, _ = make_states(blob, 2, seed=3702)
     rng = np.random.RandomState(9)
     differs = 0
@@ -684,7 +701,7 @@ def test_row_local_sweep_with_scalar_headers(blob):
         for k in range(3):
             a = rng.uniform(-1, 1, blob.act_dim).astype(np.float32)
             outs = []
-            for e in (lv, lvs, cap, reg):
+            for e in (wide, lvs, cap, reg):
                 se = s.copy()
                 obs, rew, done, info, _ = e.step(se, a)
                 outs.append((se, obs, rew, info))

@@ -1,5 +1,5 @@
 """GPU box: FeedingJaco states after a short rollout, for a bit-for-bit comparison of two builds of the solve path that do the same arithmetic
-(e.g. the row-local sweep with its headers in LDS, csrc/agx_pgs_lv.h, and with scalar headers, csrc/agx_pgs_lvs.h).
+(e.g. the wide row-local sweep, csrc/agx_pgs_lvw.h, and the narrow one, csrc/agx_pgs_lvs.h).
 usage: AGX_LIB=<build> python tools/gpu_lv_bits.py out.npz [n_envs] [steps];  python tools/gpu_lv_bits.py --compare a.npz b.npz"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
