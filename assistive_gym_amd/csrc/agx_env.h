@@ -1091,6 +1091,39 @@ AGX_DEV void env_finish_feeding(const uint32_t* blob, float* gstate, const float
     if (CLI(c, a0, AGX_C_TAG) == AGX_TAG_FOOD && CLI(c, b0, AGX_C_TAG) == AGX_TAG_TOOL) { foodc0 = a0; tool0 = b0; tool1 = GRI(c, g, AGX_G_B1); break; }
   }
   const float spill = TKF(c, AGX_T_SPILL_DIST);
+  // The query below only asks "is some tool piece within `spill` of particle k?", and with the food on the spoon the answer is yes by centimetres --
+  // yet at this limit the separating-axis early-out of gjk_distance never fires and every lane of every pass iterates to convergence.  The AABB
+  // table above proves the common case (lane = tool piece): piece j, radius included, lies inside AABB_j, and the particle's core inside its own
+  // AABB shrunk by its radius r_k (a point for a sphere), so the separation of (k, j) is at most the farthest distance between those two boxes
+  // minus r_k.  Below spill - SPILL_PROOF_GUARD (GJK_TOL is 1e-6, f32 rounding at this scale 1e-7) the converged narrowphase decides the same
+  // way and is skipped; everything else -- the shell around the limit, fallen food, non-finite boxes (the comparisons are false) -- runs it as
+  // before.  The loop below changes neither the table nor the pose of a particle it has yet to ask about.  -DAGX_FINISH_SPILL_GJK: no shortcut
+  // (lib/variants/finishgjk.so, tests/test_gpu_step_tail.py)
+  int proven_near = 0;
+#ifndef AGX_FINISH_SPILL_GJK
+  {
+    constexpr float SPILL_PROOF_GUARD = 1e-3f, FINITE_MAX = 3.0e38f;
+    const float* AB = L + L_ARENA;
+    for (int k = 0; k < c.nfood; k++) {
+      const int fc = foodc0 + k; const float rk = CLF(c, fc, AGX_C_RADIUS);
+      bool proof = false;
+      for (int base = tool0; base < tool1; base += 64) {
+        const int tc = base + lane;
+        if (tc < tool1) {
+          float far2 = 0.f; bool finite = fabsf(rk) <= FINITE_MAX;
+          for (int q = 0; q < 3; q++) {
+            const float flo = AB[ABS * fc + q] + rk, fhi = AB[ABS * fc + 3 + q] - rk, tlo = AB[ABS * tc + q], thi = AB[ABS * tc + 3 + q];
+            finite = finite && fabsf(flo) <= FINITE_MAX && fabsf(fhi) <= FINITE_MAX && fabsf(tlo) <= FINITE_MAX && fabsf(thi) <= FINITE_MAX;
+            const float up = thi - flo, down = fhi - tlo, m = up > down ? up : down;
+            far2 += m * m;
+          }
+          proof = proof || (finite && sqrtf(far2) - rk < spill - SPILL_PROOF_GUARD);
+        }
+      }
+      if (wave_any(proof)) proven_near |= 1 << k;
+    }
+  }
+#endif
   for (int k = 0; k < c.nfood; k++) {
     if (!(alive >> k & 1)) continue;
     const int b = food0 + k; float* r = L + L_ST + c.s_free + 13 * b;
@@ -1106,8 +1139,8 @@ AGX_DEV void env_finish_feeding(const uint32_t* blob, float* gstate, const float
       wave_sync();
       continue;
     }
-    bool near = false;
-    {
+    bool near = proven_near >> k & 1;
+    if (!near) {
       const int fc = foodc0 + k; const float* AB = L + L_ARENA;
       for (int base = tool0; base < tool1; base += 64) {
         const int tc = base + lane;

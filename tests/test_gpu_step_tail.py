@@ -1,0 +1,45 @@
+"""-m gpu: the tail of an env step computes the same bits as before.
+The finish kernel of the feeding variant proves the spill query ("some spoon piece within SPILL_DIST of this particle") from the collider AABBs
+where that is decided by more than a millimetre and runs the narrowphase only for the rest (csrc/agx_env.h, env_finish_feeding);
+lib/variants/finishgjk.so (-DAGX_FINISH_SPILL_GJK, built by __graft_entry__.build()) runs it for every live particle, as the kernel did up to
+round 6.  64 FeedingJaco environments -- 16 copies each of a particle resting on the spoon, in the shell around the limit (both sides), far away
+and at the mouth (tests/golden/finish_spill_cases.npz; tests/test_emu_finish_spill.py shows on the CPU which path each takes) -- stepped 8 times
+through both libraries, each in a process of its own (AGX_LIB): every output and every state record after every step is BIT-IDENTICAL."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOOL = os.path.join(ROOT, 'tools', 'gpu_step_tail_bits.py')
+FINISHGJK = os.path.join(ROOT, 'assistive_gym_amd', 'lib', 'variants', 'finishgjk.so')
+
+
+def _rollout(out, env):
+    e = dict(os.environ); e.update(env)
+    r = subprocess.run([sys.executable, TOOL, out], capture_output=True, text=True, timeout=300, env=e, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-1500:]
+    z = np.load(out)
+    return {k: z[k] for k in z.files}
+
+
+def test_spill_shortcut_bit_identical(tmp_path):
+    from assistive_gym_amd import libagx
+    if libagx.load().agx_device_count() <= 0:
+        __import__('conftest').no_gpu()
+    assert os.path.exists(FINISHGJK), 'lib/variants/finishgjk.so is missing: run __graft_entry__.build()'
+    new, old = _rollout(str(tmp_path / 'default.npz'), {}), _rollout(str(tmp_path / 'finishgjk.npz'), {'AGX_LIB': FINISHGJK})
+    for k in new:
+        rows = np.where((new[k] != old[k]).reshape(new[k].shape[0], new[k].shape[1], -1).any(axis=2))
+        assert np.array_equal(new[k], old[k]), '%s differs: (step, environment) %s' % (k, list(zip(*rows))[:8])
+    # the cases are what they are meant to be: after the first step the resting and the inner-shell particles are alive, the outer-shell and far ones
+    # spilled, the one at the mouth eaten
+    from assistive_gym_amd.blob import ModelBlob
+    blob = ModelBlob.load('feeding_jaco')
+    v = blob.view(new['state'][0].view(np.float32))
+    alive0 = v['food_alive'] & 1
+    assert alive0[:16].all() and alive0[16:32:2].all() and not alive0[17:32:2].any() and not alive0[32:].any()
+    assert (v['task_success'][48:] == 1).all() and (v['task_success'][:48] == 0).all()
