@@ -9,7 +9,7 @@
 // instead of once per substep.
 //
 // Per substep: (a) body frames, shape boxes (world AABB grown by the margin) and the attachment point into LDS; the shapes whose
-// box meets the cloth's bounding box form the candidate list, in shape order; (b) per node: normal from the incident faces,
+// box meets the bounding box of the cloth's predicted positions (computed in (b)) form the candidate list, in shape order; (b) per node: normal from the incident faces,
 // gravity, clamped aerodynamic drag, q = x, x += v dt; (c) per node: contacts with the candidate shapes (capsule / sphere cores
 // exactly, hulls through their face planes), at most AGX_CLOTH_NODE_CONTACTS per node, kept in registers -- a node's contacts
 // only move that node; (d) piterations x [anchors | rigid contacts, the links inside each wave's patch (256 neighbouring nodes: 8 of 9
@@ -198,12 +198,6 @@ __device__ inline void cloth_env(const uint32_t* blob, const float* gstate, cons
       const int ot = bi[AGX_H_OFF_TASK]; const float* B = S.body + 12 * bi[ot + AGX_T_EE_LINK];
       st(S.anchor, ld(B) + rot(B + 3, ld(bf + ot + AGX_T_EE_POS)));
     }
-    // cloth bounding box
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-#pragma unroll
-    for (int j = 0; j < NPT; j++) { const int i = own[j]; if (i >= 0) for (int a = 0; a < 3; a++) { const float v = S.x[NS4 * i + a]; lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v); } }
-    for (int a = 0; a < 3; a++) for (int o = 32; o > 0; o >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o)); }
-    if (lane == 0) for (int a = 0; a < 3; a++) { S.red[6 * wave + a] = lo[a]; S.red[6 * wave + 3 + a] = hi[a]; }
     // shape boxes: world AABB of the collider (core box rotated + radius) grown by the margin
     if (tid < NS) {
       const int* rec = cl + cl[AGX_CL_OFF_SHAPE] + 4 * tid; const int c = rec[0];
@@ -214,21 +208,6 @@ __device__ inline void cloth_env(const uint32_t* blob, const float* gstate, cons
       const float hx = fabsf(R[0]) * h.x + fabsf(R[1]) * h.y + fabsf(R[2]) * h.z + r, hy = fabsf(R[3]) * h.x + fabsf(R[4]) * h.y + fabsf(R[5]) * h.z + r,
                   hz = fabsf(R[6]) * h.x + fabsf(R[7]) * h.y + fabsf(R[8]) * h.z + r;
       float* bx = S.box + 6 * tid; bx[0] = cw.x - hx; bx[1] = cw.y - hy; bx[2] = cw.z - hz; bx[3] = cw.x + hx; bx[4] = cw.y + hy; bx[5] = cw.z + hz;
-    }
-    lds_barrier();
-    if (wave == 0) {                     // candidate list: shapes of this gender whose box meets the cloth's, in shape order
-      float clo[3], chi[3];
-      for (int a = 0; a < 3; a++) { clo[a] = S.red[a]; chi[a] = S.red[3 + a]; for (int w = 1; w < T / 64; w++) { clo[a] = fminf(clo[a], S.red[6 * w + a]); chi[a] = fmaxf(chi[a], S.red[6 * w + 3 + a]); } }
-      int n = 0;
-      for (int base = 0; base < NS; base += 64) {
-        const int sh = base + lane; bool ok = sh < NS;
-        if (ok) { const int only = cl[cl[AGX_CL_OFF_SHAPE] + 4 * sh + 3]; if (only && only != gender + 1) ok = false; }
-        if (ok) { const float* bx = S.box + 6 * sh; for (int a = 0; a < 3; a++) if (bx[a] > chi[a] || bx[3 + a] < clo[a]) ok = false; }
-        const unsigned long long m = __ballot(ok);
-        if (ok) S.cand[n + __popcll(m & ((1ull << lane) - 1ull))] = sh;
-        n += __popcll(m);
-      }
-      if (lane == 0) *S.ncand = n;
     }
     // (b) forces and prediction (normals read every node's position before any is moved: two passes with a barrier)
     f3 vnew[NPT];
@@ -255,9 +234,35 @@ __device__ inline void cloth_env(const uint32_t* blob, const float* gstate, cons
         vnew[j] = v;
       }
     }
+    // cloth bounding box of the PREDICTED positions -- the ones the contact phase tests: a garment that arrives at a shape in this substep
+    // (its box of the substep's start still clear of the shape's) has its contact in this substep, as in the oracle, not one later
+    {
+      float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+#pragma unroll
+      for (int j = 0; j < NPT; j++) {
+        const int i = own[j];
+        if (i >= 0) { const f3 xp = ldn(S.x + NS4 * i) + dt * vnew[j]; lo[0] = fminf(lo[0], xp.x); hi[0] = fmaxf(hi[0], xp.x); lo[1] = fminf(lo[1], xp.y); hi[1] = fmaxf(hi[1], xp.y); lo[2] = fminf(lo[2], xp.z); hi[2] = fmaxf(hi[2], xp.z); }
+      }
+      for (int a = 0; a < 3; a++) for (int o = 32; o > 0; o >>= 1) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o)); }
+      if (lane == 0) for (int a = 0; a < 3; a++) { S.red[6 * wave + a] = lo[a]; S.red[6 * wave + 3 + a] = hi[a]; }
+    }
     lds_barrier();
 #pragma unroll
     for (int j = 0; j < NPT; j++) { const int i = own[j]; if (i >= 0) { const f3 xi = ldn(S.x + NS4 * i); stn(S.q + NS4 * i, xi); stn(S.x + NS4 * i, xi + dt * vnew[j]); } }
+    if (wave == 0) {                     // candidate list: shapes of this gender whose box meets the cloth's, in shape order
+      float clo[3], chi[3];
+      for (int a = 0; a < 3; a++) { clo[a] = S.red[a]; chi[a] = S.red[3 + a]; for (int w = 1; w < T / 64; w++) { clo[a] = fminf(clo[a], S.red[6 * w + a]); chi[a] = fmaxf(chi[a], S.red[6 * w + 3 + a]); } }
+      int n = 0;
+      for (int base = 0; base < NS; base += 64) {
+        const int sh = base + lane; bool ok = sh < NS;
+        if (ok) { const int only = cl[cl[AGX_CL_OFF_SHAPE] + 4 * sh + 3]; if (only && only != gender + 1) ok = false; }
+        if (ok) { const float* bx = S.box + 6 * sh; for (int a = 0; a < 3; a++) if (bx[a] > chi[a] || bx[3 + a] < clo[a]) ok = false; }
+        const unsigned long long m = __ballot(ok);
+        if (ok) S.cand[n + __popcll(m & ((1ull << lane) - 1ull))] = sh;
+        n += __popcll(m);
+      }
+      if (lane == 0) *S.ncand = n;
+    }
     lds_barrier();
     // (c) contacts of this thread's nodes (CollideSDF_RS::DoNode)
 #ifdef AGXC_NO_CONTACTS

@@ -2128,6 +2128,11 @@ static void cloth_detach(sim_t* s, float* cloth) {
   for (int k = 0; k < n3; k++) { cloth[k] = (float)s->cx[k]; cloth[n3 + k] = (float)s->cv[k]; }
   free(s->cx); free(s->cv); free(s->cq); free(s->ccon); free(s->ccon_node); free(s->ccon_shape); s->cx = NULL;
 }
+/* the contacts of the last cloth substep of the last agxo_step_cloth / agxo_settle_cloth call (agxo_cloth_contacts) */
+static double g_ccon[6 * 4096]; static int g_ccon_node[4096]; static int g_nccon = 0;
+static void cloth_contacts_keep(const sim_t* s) {
+  g_nccon = s->cx ? (s->nccon < 4096 ? s->nccon : 4096) : 0; if (g_nccon) { memcpy(g_ccon, s->ccon, sizeof(double) * 6 * g_nccon); memcpy(g_ccon_node, s->ccon_node, sizeof(int) * g_nccon); }
+}
 void agxo_settle_cloth(const agxo_model* m, float* state, float* cloth, int n_sim_steps) {
   sim_t* s = (sim_t*)malloc(sizeof *s); sim_load(s, m, state);
   s->rows = (row_t*)malloc(sizeof(row_t) * MAXROWS);
@@ -2135,12 +2140,12 @@ void agxo_settle_cloth(const agxo_model* m, float* state, float* cloth, int n_si
   s->settling = 1;
   for (int k = 0; k < n_sim_steps; k++) sim_step(s);
   kinematics(s); update_target(s);
+  if (n_sim_steps > 0) cloth_contacts_keep(s);
   cloth_detach(s, cloth);
   sim_store(s, state); free(s->rows); free(s);
 }
 void agxo_settle(const agxo_model* m, float* state, int n_substeps) { agxo_settle_cloth(m, state, NULL, n_substeps); }
 /* contacts of the cloth with the rigid shapes in the last substep of the last call: {x, y, z, fx, fy, fz} each (tests) */
-static double g_ccon[6 * 4096]; static int g_ccon_node[4096]; static int g_nccon = 0;
 int agxo_cloth_contacts(double* out, int max_out) { int n = g_nccon < max_out ? g_nccon : max_out; memcpy(out, g_ccon, sizeof(double) * 6 * n); return g_nccon; }
 /* ... and the garment node of each of them (tests/test_gpu_bench_size.py: which node contacts are in the cloth-force sum on either side) */
 int agxo_cloth_contact_nodes(int* out, int max_out) { int n = g_nccon < max_out ? g_nccon : max_out; memcpy(out, g_ccon_node, sizeof(int) * n); return g_nccon; }
@@ -2187,7 +2192,7 @@ void agxo_step_cloth(const agxo_model* m, float* state, float* cloth, const floa
   kinematics(s); /* poses after the last integration, as the getters in _get_obs see them */
   if (m->task_kind == AGX_TASK_DRESSING) {
     finish_dressing(s, action, obs, reward, done, info);
-    g_nccon = s->cx ? (s->nccon < 4096 ? s->nccon : 4096) : 0; if (g_nccon) { memcpy(g_ccon, s->ccon, sizeof(double) * 6 * g_nccon); memcpy(g_ccon_node, s->ccon_node, sizeof(int) * g_nccon); }
+    cloth_contacts_keep(s);
     cloth_detach(s, cloth); sim_store(s, state); free(s->rows); free(s); return;
   }
   if (m->task_kind == AGX_TASK_DRINKING) { finish_drinking(s, act_norm2, obs, reward, done, info); cloth_detach(s, cloth); sim_store(s, state); free(s->rows); free(s); return; }
