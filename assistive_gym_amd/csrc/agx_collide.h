@@ -152,6 +152,109 @@ AGX_DEV bool face_point(const Ctx& c, int ca, int cb, int e, v3 p0, Cand& out) {
   out.n = mk3(0.f, 0.f, 1.f); out.pa = mk3(pick.x, pick.y, pick.z - ra); out.pb = mk3(pick.x, pick.y, top); out.dist = pick.z - ra - top;
   return true;
 }
+// AGX_FACE.  What the face pairs of a pass cost is a chain of memory round trips, and most of it buys nothing:
+//   * face_point above walks the hull one vertex per loop round (zmin, the first-in-band search, one farthest-point loop per extra contact), each
+//     round waiting for its own 12-byte blob load, and the lanes sub = 1..3 of a pair each repeat the zmin scan of lane sub = 0;
+//   * entry 0 of the pair runs GJK to convergence (5-6 iterations, the longest of the substep, two served hull scans each), and when it hits with
+//     n.z > 0.999 everything GJK computed is overwritten by face_point(.., 0, ..): two booleans survive.
+// 1: face_point_wide below -- the same comparisons in the same order over EIGHT vertices per round (the load pattern of gjk_support, indices
+//    clamped to n - 1: a repeated vertex never wins a strict comparison and cannot be the first in the band before itself), every value that
+//    leaves the function taken from `R v + p` on a fresh 12-byte load by index, the first-in-band search still ending at the round that finds
+//    one; zmin computed once per pair, by lane sub = 0, and handed to the pair's other entries through word 0 of their own CD[] slots (which
+//    they overwrite at the end of their pass, also across a pass boundary).  The first contact is computed BEFORE narrowphase() (it never looked
+//    at GJK's point) and parked in the lane's own CD[] slot.
+// 2 (the DEFAULT): as 1, and a lane whose pair is provably a face contact does not run GJK at all (collide_flush).
+// 0 (or -DAGX_FACE_PLAIN): GJK for every pair and the one-vertex loops, as before this switch existed (lib/variants/faceplain.so; tests/test_gpu_face_proof.py
+//    and tests/test_emu_face_proof.py compare the bits).
+#ifdef AGX_FACE_PLAIN
+#undef AGX_FACE
+#define AGX_FACE 0
+#endif
+#ifndef AGX_FACE
+#define AGX_FACE 2
+#endif
+#if AGX_FACE < 0 || AGX_FACE > 2
+#error "AGX_FACE: 0, 1 or 2"
+#endif
+// The proof of value 2, for entry 0 of a face_box pair (A a hull of >= 2 vertices, B the static box), from the AB[] boxes and the zmin that
+// face_point_wide has just computed from A's vertices.  With every comparison below true:
+//   footprint: A's world box lies inside B's in x and y by FACE_PROOF_GUARD.  A's core vertices lie inside A's box (radius and travel only widen
+//     it), so all of them are inside B's footprint -- zmin is the minimum over ALL vertices and face_point finds its first contact -- and inside
+//     the footprint of the clipped box narrowphase() builds (B's box cut to A's box grown by AGX_BOX_CLIP); that box is not empty (the z test).
+//   gap: dcore = zmin - top > FACE_PROOF_GUARD: every core vertex is above the box's top face and over it, so in exact arithmetic the core
+//     distance IS dcore, attained along +z.  |v| never falls below the true distance during the iteration: no `vv < 1e-12` exit (1e-6 m), no
+//     enclosed origin, no penetration sampler.
+//   limit: dcore - r_a - r_b < lim - FACE_PROOF_GUARD_LIM.  At the tolerance exit of gjk_distance (vv - vw <= GJK_TOL vv, GJK_TOL = 1e-6) v.w <= |v| d for
+//     the true distance d, so |v| <= d / (1 - GJK_TOL): 6e-9 m too long at these 6 mm, and v within sqrt(GJK_TOL) = 1e-3 rad of +z, n.z >= 1 - 5e-7.
+//     The lower bounds of the separating-axis exit never exceed d, and it fires GJK_FAR_MARGIN = 1e-4 beyond the limit only.
+// Rounding: GJK works in a frame shifted to A's box (coordinates of centimetres, 1e-8), but the shift, the body position and the box are world
+// coordinates (|x| < 2 m: 1.2e-7 each), as are zmin and the AB[] boxes used here: a few times 1e-7 in all, with the 6e-9 above.
+// FACE_PROOF_GUARD = GJK_FAR_MARGIN = 1e-4 (a thousand roundings, a hundred times the 1e-6 m of the `vv < 1e-12` exit) for the footprint and the
+// lower side of the gap, where a resting piece clears it by millimetres; FACE_PROOF_GUARD_LIM = 1e-5 (some thirty roundings; the same allowance
+// as the 1e-5 in the limits of collide_flush and collide_sweep) towards the limit, because that is where the pieces of a resting bowl ARE: its
+// upper ring sits 5.87 mm above the table under a limit of 5.93 mm.  With all of this GJK would converge to a hit with n.z > 0.999 and its numbers
+// would be overwritten: the lane skips it.  For the other exits of gjk_distance (a repeated support point, no
+// progress, maxit) there is no such argument; the bit comparisons of the two test files at volume are the check.  Anything else -- a piece
+// overhanging an edge, tilted off its footprint, in the shell around either guard, overlapping cores, non-finite numbers (the comparisons are
+// false), no first contact -- runs GJK as before.
+constexpr float FACE_PROOF_GUARD = 1e-4f, FACE_PROOF_GUARD_LIM = 1e-5f;
+
+#if AGX_FACE
+// face_point with the wide loops.  e = 0: computes zmin (3e38 if no vertex is above the footprint) and the first contact; e >= 1: takes zmin from the caller.
+AGX_DEV bool face_point_wide(const Ctx& c, int ca, int cb, int e, v3 p0, float& zmin, Cand& out) {
+  const float* AB = c.lds + L_ARENA;
+  const int n = CLI(c, ca, AGX_C_NVERT), last = n - 1;
+  const float* V = c.bf + c.o_vert + 3 * CLI(c, ca, AGX_C_VOFF);
+  m3 R; v3 p; body_xf(c, CLI(c, ca, AGX_C_BODY), R, p);
+  const float x0 = AB[ABS * cb], y0 = AB[ABS * cb + 1], x1 = AB[ABS * cb + 3], y1 = AB[ABS * cb + 4], top = AB[ABS * cb + 5];   // radius included
+#define FACE_LDV(j, kk) const int i##j = (kk) < last ? (kk) : last; const float vx##j = V[3 * i##j], vy##j = V[3 * i##j + 1], vz##j = V[3 * i##j + 2];
+#define FACE_LD8(k) FACE_LDV(0, k) FACE_LDV(1, k + 1) FACE_LDV(2, k + 2) FACE_LDV(3, k + 3) FACE_LDV(4, k + 4) FACE_LDV(5, k + 5) FACE_LDV(6, k + 6) FACE_LDV(7, k + 7)
+#define FACE_W(j) const v3 w = mul(R, mk3(vx##j, vy##j, vz##j)) + p; const bool in = w.x >= x0 && w.x <= x1 && w.y >= y0 && w.y <= y1;
+#define FACE_ALL8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+#define FACE_FRESH(i) (mul(R, mk3(V[3 * (i)], V[3 * (i) + 1], V[3 * (i) + 2])) + p)
+  float cx[1 + AGX_FACE_EXTRA], cy[1 + AGX_FACE_EXTRA];
+  cx[0] = p0.x; cy[0] = p0.y;
+#pragma unroll
+  for (int q = 1; q <= AGX_FACE_EXTRA; q++) { cx[q] = 0.f; cy[q] = 0.f; }
+  v3 pick = mk3(0.f, 0.f, 0.f);
+  if (e == 0) {
+    int iz = -1; float zm = 3.0e38f;
+#define FACE_ZMIN(j) { FACE_W(j) const bool t = in && w.z < zm; zm = t ? w.z : zm; iz = t ? i##j : iz; }
+    for (int k = 0; k < n; k += 8) { FACE_LD8(k) FACE_ALL8(FACE_ZMIN) }
+#undef FACE_ZMIN
+    zmin = 3.0e38f;
+    if (iz < 0) return false;
+    zmin = FACE_FRESH(iz).z;
+    int first = -1;   // the first vertex (model order) inside the band
+#define FACE_BAND(j) { FACE_W(j) const bool t = first < 0 && in && w.z <= zmin + AGX_FACE_BAND; first = t ? i##j : first; }
+    for (int k = 0; k < n && first < 0; k += 8) { FACE_LD8(k) FACE_ALL8(FACE_BAND) }
+#undef FACE_BAND
+    if (first < 0) return false;
+    pick = FACE_FRESH(first);
+  }
+#pragma unroll
+  for (int q = 1; q <= AGX_FACE_EXTRA; q++) {
+    if (q > e) break;
+    int bi = -1; float bd = AGX_FACE_SPREAD * AGX_FACE_SPREAD;
+#define FACE_FAR(j) { FACE_W(j) float dmin = 3.0e38f; \
+      _Pragma("unroll") for (int kk = 0; kk <= AGX_FACE_EXTRA; kk++) if (kk < q) { const float dx = w.x - cx[kk], dy = w.y - cy[kk]; dmin = fminf(dmin, dx * dx + dy * dy); } \
+      const bool t = in && !(w.z > zmin + AGX_FACE_BAND) && dmin > bd; bd = t ? dmin : bd; bi = t ? i##j : bi; }
+    for (int k = 0; k < n; k += 8) { FACE_LD8(k) FACE_ALL8(FACE_FAR) }
+#undef FACE_FAR
+    if (bi < 0) return false;
+    const v3 bw = FACE_FRESH(bi);
+    cx[q] = bw.x; cy[q] = bw.y; pick = bw;
+  }
+#undef FACE_LDV
+#undef FACE_LD8
+#undef FACE_W
+#undef FACE_ALL8
+#undef FACE_FRESH
+  const float ra = CLF(c, ca, AGX_C_RADIUS);
+  out.n = mk3(0.f, 0.f, 1.f); out.pa = mk3(pick.x, pick.y, pick.z - ra); out.pb = mk3(pick.x, pick.y, top); out.dist = pick.z - ra - top;
+  return true;
+}
+#endif
 struct CollideState { int ncon, near_mask, overflow, maxc, nqpt; };
 // the pair-group table, one group per lane (lane g = group g): read from the blob once per substep and
 // broadcast with v_readlane where a group's parameters are needed (a dependent blob load costs an L2 trip)
@@ -241,17 +344,55 @@ AGX_DEV void collide_flush(Ctx& c, int wn, CollideState& cs, float brk, float sl
       if (!(GRI(c, g, AGX_G_FLAGS) & (2 | 64))) lim = fminf(brk, slack + rel_travel(c, a, b) + 1e-5f);
     }
     k.n = mk3(0.f, 0.f, 0.f); k.pa = k.n; k.pb = k.n; k.dist = 0.f;
+#if AGX_FACE
+    // entry 0 of a face pair (AGX_FACE above): the re-anchored first contact, parked in the lane's CD[] slot (point, distance, and in word 0
+    // whether there is one -- 1 -- and whether the pair is proven to be a face contact -- 2) until GJK, or the proof, says that it is one;
+    // zmin to the pair's other entries.  (Parked in LDS, not in registers: nothing of this is live across gjk_distance.)
+    bool proven = false;
+    if (has && sub == 0) {
+      float* cd = CD + CAND_STRIDE * i; float state = 0.f;
+      if (face_box(c, b) && CLI(c, a, AGX_C_NVERT) >= 2) {
+        Cand k0; k0.pa = k.pa; k0.dist = 0.f; float zmin;
+        const bool first = face_point_wide(c, a, b, 0, k.pa, zmin, k0);
+        st3(cd + 1, k0.pa); cd[7] = k0.dist;
+#pragma unroll
+        for (int q = 1; q <= AGX_FACE_EXTRA; q++) if (i + q < wn) CD[CAND_STRIDE * (i + q)] = zmin;
+        state = first ? 1.f : 0.f;
+#if AGX_FACE >= 2
+        const float* Aa = AB + ABS * a; const float* Bb = AB + ABS * b; const float top = Bb[5], dcore = zmin - top;
+        proven = first && Aa[0] >= Bb[0] + FACE_PROOF_GUARD && Aa[3] <= Bb[3] - FACE_PROOF_GUARD && Aa[1] >= Bb[1] + FACE_PROOF_GUARD && Aa[4] <= Bb[4] - FACE_PROOF_GUARD &&
+                 Aa[0] <= Aa[3] && Aa[1] <= Aa[4] && Aa[2] - AGX_BOX_CLIP <= top && Aa[5] + AGX_BOX_CLIP >= top && Bb[2] <= top &&
+                 dcore > FACE_PROOF_GUARD && dcore - CLF(c, a, AGX_C_RADIUS) - CLF(c, b, AGX_C_RADIUS) < lim - FACE_PROOF_GUARD_LIM;
+        if (proven) state = 2.f;
+#endif
+      }
+      cd[0] = state;
+    }
+    bool hit = narrowphase(c, a, b, lim, k, has && sub == 0 && !proven);
+    if (has && sub == 0) {
+      const float* cd = CD + CAND_STRIDE * i; const float state = cd[0];
+      if (state == 2.f || (state == 1.f && hit && k.n.z > 0.999f)) {
+        hit = true; k.n = mk3(0.f, 0.f, 1.f); k.pa = ld3(cd + 1); k.pb = mk3(k.pa.x, k.pa.y, AB[ABS * b + 5]); k.dist = cd[7];
+      }
+    }
+#else
     bool hit = narrowphase(c, a, b, lim, k, has && sub == 0);
     // (timed with every narrowphase run twice, round 4: 473 -> 427 k env-steps/s, the ceiling of any gain here; profiles/r04/r04u_ab_feeding_narrowphase_twice.txt)
     // on a face GJK's closest point is an arbitrary point of the face: the first contact of a pair resting on a static
     // world box is re-anchored at a vertex as well (oracle: face_manifold)
     if (has && sub == 0 && hit && k.n.z > 0.999f && face_box(c, b) && CLI(c, a, AGX_C_NVERT) >= 2) { Cand k0; k0.gap = k.gap; if (face_point(c, a, b, 0, k.pa, k0)) k = k0; }
+#endif
     if (wave_any(has && sub > 0)) {   // face-manifold entries: the GJK contact of the pair is `sub` entries back
       if (has && sub == 0) { float* cd = CD + CAND_STRIDE * i; st3(cd + 1, k.pa); st3(cd + 4, k.n); }
       wave_sync();
       if (has && sub > 0) {
         const float* sd = CD + CAND_STRIDE * (i - sub);
+#if AGX_FACE
+        float zmin = CD[CAND_STRIDE * i];
+        hit = sd[6] > 0.999f && face_point_wide(c, a, b, sub, ld3(sd + 1), zmin, k) && k.dist < brk;
+#else
         hit = sd[6] > 0.999f && face_point(c, a, b, sub, ld3(sd + 1), k) && k.dist < brk;
+#endif
       }
     }
     if (has) {
