@@ -1,7 +1,7 @@
 """Build libagx.so (HIP, gfx950) in-tree.  `python -m assistive_gym_amd.build`.
 
 The kernels are compiled once per variant (limits + task layer, csrc/agx_kernels.hip) and linked with the handle /
-C-ABI code (csrc/agx_api.hip)."""
+C-ABI code (csrc/agx_api.hip) and the policy-step / GAE kernels (csrc/agx_policy.hip)."""
 import os
 import subprocess
 import sys
@@ -28,7 +28,8 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
         base.append('-Rpass-analysis=kernel-resource-usage')
     objdir = os.path.join(HERE, 'lib', 'obj' if not out else 'obj_' + os.path.splitext(os.path.basename(out))[0])
     os.makedirs(objdir, exist_ok=True)
-    jobs = [(os.path.join(objdir, 'agx_api.o'), base + ['-c', os.path.join(CSRC, 'agx_api.hip')])]
+    jobs = [(os.path.join(objdir, 'agx_api.o'), base + ['-c', os.path.join(CSRC, 'agx_api.hip')]),
+            (os.path.join(objdir, 'agx_policy.o'), base + ['-c', os.path.join(CSRC, 'agx_policy.hip')])]      # policy step + GAE (stateless entries)
     reuse = []
     for v in VARIANTS:
         if only and v not in only:
@@ -37,6 +38,7 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
         jobs.append((os.path.join(objdir, 'agx_kernels_%s.o' % v.lower()), base + ['-DAGX_VARIANT_' + v, '-c', os.path.join(CSRC, 'agx_kernels.hip')]))
     if only:
         jobs[0] = (os.path.join(HERE, 'lib', 'obj', 'agx_api.o'), None)
+        jobs[1] = (os.path.join(HERE, 'lib', 'obj', 'agx_policy.o'), None)
     with ThreadPoolExecutor(len(jobs)) as ex:
         list(ex.map(lambda j: j[1] and subprocess.check_call(j[1] + ['-o', j[0]]), jobs))
     subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + [j[0] for j in jobs] + reuse)

@@ -15,7 +15,7 @@ EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_p
            'agx_set_state', 'agx_get_state', 'agx_state_dev', 'agx_settle', 'agx_settle_debug', 'agx_cloth_nodes', 'agx_set_cloth', 'agx_get_cloth', 'agx_cloth_dev', 'agx_set_cloth_pool', 'agx_get_cloth_report', 'agx_step', 'agx_step_debug', 'agx_step_timed', 'agx_debug_words',
            'agx_observe', 'agx_observe_masked', 'agx_reset_done_at', 'agx_sample_reset', 'agx_reset', 'agx_attach_settle_model', 'agx_reset_done', 'agx_step_host', 'agx_observe_host', 'agx_profile_begin', 'agx_profile_end',
            'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_set_env_offset', 'agx_check_collisions',
-           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step']
+           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae']
 
 
 class AgxError(RuntimeError):
@@ -31,6 +31,9 @@ def load():
         L.agx_version.restype = C.c_char_p
         L.agx_last_error.restype = C.c_char_p
         L.agx_variant_name.restype = C.c_char_p
+        L.agx_policy_act.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_longlong, C.c_uint32, C.c_int,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.agx_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -58,6 +61,32 @@ def comm_init_rank(device, rank, world, unique_id):
 def comm_destroy(comm):
     if comm:
         check(load().agx_comm_destroy(C.c_void_p(comm)), 'agx_comm_destroy')
+
+
+POLICY_MAX_IN, POLICY_MAX_ACT, POLICY_TILE = 128, 32, 16      # agx_policy_act: largest obs_dim / hidden width, largest act_dim, environments per workgroup
+_STATELESS_ERRORS = {-1: 'an argument is outside the limits of include/agx.h', -3: 'the launch failed', -4: 'no HIP device (libagx has no CPU path)'}
+
+
+def _check_stateless(rc, what):
+    if rc != 0:                                            # the stateless entries report by return code only
+        raise AgxError('%s failed (%d): %s' % (what, rc, _STATELESS_ERRORS.get(rc, '?')))
+
+
+def policy_act(params, obs_dim, hidden_a, hidden_b, act_dim, obs, n_envs, seed, env_offset, step, action, logp, value, deterministic=False, stream=0):
+    """agx_policy_act on the current device of the calling thread.  params: flat float32 device tensor (GaussianMLPPolicy.flat_params);
+    obs / action: float32 device tensors whose rows are the environments -- views of wider tensors are fine, their row stride is passed on;
+    logp / value: contiguous [n_envs]"""
+    assert obs.stride(-1) == 1 and action.stride(-1) == 1 and logp.is_contiguous() and value.is_contiguous()
+    _check_stateless(load().agx_policy_act(params.data_ptr(), obs_dim, hidden_a, hidden_b, act_dim, obs.data_ptr(), obs.stride(0), n_envs,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), int(step) & 0xFFFFFFFF, int(bool(deterministic)),
+                                           action.data_ptr(), action.stride(0), logp.data_ptr(), value.data_ptr(), stream or None), 'agx_policy_act')
+
+
+def gae(rewards, values, dones, gamma, lam, adv, ret, stream=0):
+    """agx_gae: contiguous float32 device tensors rewards / adv / ret [T, N], values [T + 1, N], dones uint8 [T, N]"""
+    T, N = rewards.shape
+    assert values.shape == (T + 1, N) and dones.shape == (T, N) and all(x.is_contiguous() for x in (rewards, values, dones, adv, ret))
+    _check_stateless(load().agx_gae(rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), T, N, gamma, lam, adv.data_ptr(), ret.data_ptr(), stream or None), 'agx_gae')
 
 
 def _ptr(x):
