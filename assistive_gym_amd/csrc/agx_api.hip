@@ -560,7 +560,8 @@ int agx_get_cloth(agx_handle h, float* host_cloth) {
 int agx_cloth_dev(agx_handle h, float** out_dev) { if (!h || !out_dev || !h->cloth_dev) return fail(AGX_E_ARG, "agx_cloth_dev: bad argument or a model without a cloth"); *out_dev = h->cloth_dev; return AGX_OK; }
 int agx_get_cloth_report(agx_handle h, float* host_report, int* words_per_env) {
   if (!h || !h->cloth_dev || !h->report_dev) return fail(AGX_E_ARG, "agx_get_cloth_report: bad argument or a model without a cloth");
-  const int words = AGX_CLOTH_REPORT_WORDS(h->cloth_nn);
+  // a particle section's report is the water kernel's: one word per particle slot (agx_water.h REPORT_WORDS), the whole row
+  const int words = h->particles ? h->report_words : AGX_CLOTH_REPORT_WORDS(h->cloth_nn);
   if (words_per_env) *words_per_env = words;
   if (!host_report) return AGX_OK;
   HIPCHK(hipSetDevice(h->device));

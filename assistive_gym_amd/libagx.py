@@ -110,6 +110,8 @@ class Stepper:
         self.h = h
         self.n_envs, self.device = n_envs, device
         self.act_dim, self.obs_dim, self.state_words = blob.act_dim, blob.obs_dim, blob.state_words
+        from .model import compiler as L
+        self.particles = bool(blob.h.get('OFF_CLOTH', 0) and int(blob.i[blob.h['OFF_CLOTH'] + L.CL['PARTICLES']]))      # the water of a drinking scene (agx_water.h)
 
     def close(self):
         if getattr(self, 'h', None):
@@ -125,9 +127,7 @@ class Stepper:
     def n_chunks(self):
         """independent chunks of environments a step is issued as (AGX_CHUNKS, default 3 from 2048 environments on)"""
         e = os.environ.get('AGX_CHUNKS')
-        from .model import compiler as L
-        particles = self.blob.h.get('OFF_CLOTH', 0) and int(self.blob.i[self.blob.h['OFF_CLOTH'] + L.CL['PARTICLES']])     # the drinking scenes run unchunked (agx_api.hip)
-        nc = int(e) if e else (1 if particles else (3 if self.n_envs >= 2048 else 1))
+        nc = int(e) if e else (1 if self.particles else (3 if self.n_envs >= 2048 else 1))
         nc = min(max(nc, 1), 8)
         return 1 if self.n_envs < 64 * nc else nc
 
@@ -193,12 +193,13 @@ class Stepper:
 
     def get_cloth_report(self):
         """the cloth kernel's report of the last step, float32 [n_envs, 20 + 2 * slots * nodes]: sleeve vertices (18), 2 unused, then per node and
-        contact slot {node height, |contact force| of the last substep or -1} (agx_get_cloth_report)"""
+        contact slot {node height, |contact force| of the last substep or -1} (agx_get_cloth_report).  A drinking handle (particle section):
+        int32 [n_envs, 64], per particle 1 = touched the person in the last internal substep"""
         w = C.c_int()
         check(self.L.agx_get_cloth_report(self.h, None, C.byref(w)), 'agx_get_cloth_report')
         out = np.zeros((self.n_envs, w.value), dtype=np.float32)
         check(self.L.agx_get_cloth_report(self.h, out.ctypes.data_as(C.c_void_p), None), 'agx_get_cloth_report')
-        return out
+        return out.view(np.int32) if self.particles else out
 
     def set_cloth_pool(self, pool_cloth):
         """pool_cloth: float32 device tensor [pool_n, 2, nodes, 3]; the caller keeps it alive"""

@@ -84,7 +84,9 @@ int agx_set_cloth_pool(agx_handle h, const float* pool_cloth_dev);
  * (util.py:156-157), 2 unused, then per node and contact slot {height of the node, |contact force| of the last substep, -1 = no contact}
  * (what dressing.py:25,35-43 reads from getSoftBodyData; AGX_CLOTH_REPORT_WORDS in agx_blob.h).  words_per_env (may be NULL) receives the row
  * length; host_report NULL = query the length only.  Synchronises the device.  For parity tests of the cloth-force term (which node contacts
- * are in the sum), not on the step path. */
+ * are in the sum), not on the step path.
+ * Models with a particle section (the water of the drinking scenes): the row is 64 words, int32 behind the float pointer -- per particle 1
+ * when it touched a shape of the person in the LAST internal substep of the last agx_step / agx_settle, else 0; 0 beyond the last particle. */
 int agx_get_cloth_report(agx_handle h, float* host_report, int* words_per_env);
 int agx_debug_words(void);   /* of the FeedingJaco kernel variant; agx_debug_layout for the variant serving a handle */
 /* layout of the debug record of the kernel variant serving this handle: out8 = {words per env, contacts offset, M^-1 offset,

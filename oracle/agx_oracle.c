@@ -1381,7 +1381,7 @@ static void cloth_substep(sim_t* s) {
  * scene like the garment (they see the cup, the gripper and the person where this substep starts).  Position-based, every step local to a
  * particle or a Jacobi pass, so that a device kernel with one lane per particle reproduces it:
  *   1. v += g dt, x = q + v dt;
- *   2. candidate shapes per particle (at most WATER_CONTACTS, in shape order): those within 2 r + |v| dt of where the substep starts; each
+ *   2. candidate shapes per particle (at most WATER_CONTACTS, in shape order; none for a particle beyond 500 m): those within 2 r + |v| dt of where the substep starts; each
  *      contributes the half space of the face (or tangent plane) the particle is in front of THERE;
  *   3. PITER iterations: (a) particle <-> particle: every particle sums, over its overlapping neighbours in ascending index order and from
  *      the positions the pass starts with, half of each overlap along the centre line, divides by their number and moves by that; (b) each
@@ -1413,7 +1413,9 @@ static void water_substep(sim_t* s) {
     for (int k = 0; k < 3; k++) q[i][k] = x[i][k];
     v[i][2] += s->dr_gravity * dt;
     const double reach = 2 * r + sqrt(dot3(v[i], v[i])) * dt;
-    for (int sh = 0; sh < NS && ncand[i] < WATER_CONTACTS; sh++) {
+    /* a "drunk" particle waits thousands of metres away (drinking.py:70): beyond 500 m it has no candidates, as in the kernel */
+    const int here = fabs(q[i][0]) < 500 && fabs(q[i][1]) < 500 && fabs(q[i][2]) < 500;
+    for (int sh = 0; here && sh < NS && ncand[i] < WATER_CONTACTS; sh++) {
       const int only = m->i[oc + CLH(m, AGX_CL_OFF_SHAPE) + 4 * sh + 3];
       if (only && only != s->gender + 1) continue;
       int out = 0; for (int k = 0; k < 3; k++) if (q[i][k] < slo[sh][k] - reach || q[i][k] > shi[sh][k] + reach) out = 1;
@@ -2129,9 +2131,9 @@ static void cloth_detach(sim_t* s, float* cloth) {
   free(s->cx); free(s->cv); free(s->cq); free(s->ccon); free(s->ccon_node); free(s->ccon_shape); s->cx = NULL;
 }
 /* the contacts of the last cloth substep of the last agxo_step_cloth / agxo_settle_cloth call (agxo_cloth_contacts) */
-static double g_ccon[6 * 4096]; static int g_ccon_node[4096]; static int g_nccon = 0;
+static double g_ccon[6 * 4096]; static int g_ccon_node[4096]; static int g_ccon_shape[4096]; static int g_nccon = 0;
 static void cloth_contacts_keep(const sim_t* s) {
-  g_nccon = s->cx ? (s->nccon < 4096 ? s->nccon : 4096) : 0; if (g_nccon) { memcpy(g_ccon, s->ccon, sizeof(double) * 6 * g_nccon); memcpy(g_ccon_node, s->ccon_node, sizeof(int) * g_nccon); }
+  g_nccon = s->cx ? (s->nccon < 4096 ? s->nccon : 4096) : 0; if (g_nccon) { memcpy(g_ccon, s->ccon, sizeof(double) * 6 * g_nccon); memcpy(g_ccon_node, s->ccon_node, sizeof(int) * g_nccon); memcpy(g_ccon_shape, s->ccon_shape, sizeof(int) * g_nccon); }
 }
 void agxo_settle_cloth(const agxo_model* m, float* state, float* cloth, int n_sim_steps) {
   sim_t* s = (sim_t*)malloc(sizeof *s); sim_load(s, m, state);
@@ -2149,6 +2151,8 @@ void agxo_settle(const agxo_model* m, float* state, int n_substeps) { agxo_settl
 int agxo_cloth_contacts(double* out, int max_out) { int n = g_nccon < max_out ? g_nccon : max_out; memcpy(out, g_ccon, sizeof(double) * 6 * n); return g_nccon; }
 /* ... and the garment node of each of them (tests/test_gpu_bench_size.py: which node contacts are in the cloth-force sum on either side) */
 int agxo_cloth_contact_nodes(int* out, int max_out) { int n = g_nccon < max_out ? g_nccon : max_out; memcpy(out, g_ccon_node, sizeof(int) * n); return g_nccon; }
+/* ... and the entry of the section's shape table (tests/test_water_kernel_cases.py: which particle touched which shape) */
+int agxo_cloth_contact_shapes(int* out, int max_out) { int n = g_nccon < max_out ? g_nccon : max_out; memcpy(out, g_ccon_shape, sizeof(int) * n); return g_nccon; }
 
 void agxo_step(const agxo_model* m, float* state, const float* action, float* obs, float* reward, int* done, float* info) {
   agxo_step_cloth(m, state, NULL, action, obs, reward, done, info);

@@ -40,6 +40,7 @@ int agxo_cloth_nodes(const agxo_model* m);
 void agxo_step_cloth(const agxo_model* m, float* state, float* cloth, const float* action, float* obs, float* reward, int* done, float* info);
 void agxo_settle_cloth(const agxo_model* m, float* state, float* cloth, int n_sim_steps);
 int agxo_cloth_contacts(double* out, int max_out);
+int agxo_cloth_contact_shapes(int* out, int max_out);   /* shape-table entry of each of them */
 /* observation only (reset() return value, feeding.py:182) */
 void agxo_observe(const agxo_model* m, const float* state, float* obs);
 

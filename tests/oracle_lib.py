@@ -122,6 +122,13 @@ class Oracle:
         n = self.L.agxo_cloth_contact_nodes(_p(out), C.c_int(max_out))
         return out[:min(n, max_out)]
 
+    def cloth_contact_shapes(self, max_out=4096):
+        """entry of the cloth section's shape table of every contact of cloth_contacts()"""
+        out = np.zeros(max_out, dtype=np.int32)
+        self.L.agxo_cloth_contact_shapes.restype = C.c_int
+        n = self.L.agxo_cloth_contact_shapes(_p(out), C.c_int(max_out))
+        return out[:min(n, max_out)]
+
     def manifold_get(self):
         """the cached points: rows {collider a, collider b, local point on A (3), on B (3), world normal (3), friction}"""
         out = np.zeros((64, 12))
