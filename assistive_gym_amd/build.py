@@ -1,41 +1,44 @@
 """Build libagx.so (HIP, gfx950) in-tree.  `python -m assistive_gym_amd.build`.
 
-The kernels are compiled once per variant (limits + task layer, csrc/agx_kernels.hip) and linked with the handle /
+The kernels are compiled once per variant (limits + task layer: one line of csrc/agx_variants.def, csrc/agx_kernels.hip) and linked with the handle /
 C-ABI code (csrc/agx_api.hip) and the policy-step / GAE kernels (csrc/agx_policy.hip)."""
 import os
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from . import variants
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-DEPS = [os.path.join(CSRC, f) for f in sorted(f for f in os.listdir(CSRC) if f.endswith(('.h', '.hip')))] + \
+DEPS = [os.path.join(CSRC, f) for f in sorted(f for f in os.listdir(CSRC) if f.endswith(('.h', '.hip', '.def')))] + \
        [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('agx.h', 'agx_blob.h')]
 OUT = os.path.join(HERE, 'lib', 'libagx.so')
-VARIANTS = ['FEEDING', 'FEEDING_L', 'FEEDING_M', 'BED_BATHING', 'BED_BATHING_L', 'BED_BATHING_M', 'SCRATCH_ITCH', 'SCRATCH_ITCH_M', 'BED_SETTLE', 'DRESSING', 'DRESSING_L', 'DRESSING_M', 'ARM_MANIPULATION', 'ARM_MANIPULATION_L', 'DRINKING', 'DRINKING_L', 'DRINKING_M']
 
 
 def build(force=False, verbose=False, extra=(), out=None, only=None):
-    """out / extra: an A/B build of the same library with extra compiler flags (same-box comparisons: AGX_LIB=<out> python bench.py);
-    only: kernel variants the extra flags apply to (e.g. ['FEEDING']) -- the other objects are taken from the main build's lib/obj"""
+    """out / extra: an A/B build of the same library with extra compiler flags (same-box comparisons: AGX_LIB=<out> python bench.py); they follow the
+    variant's own -D flags, so an extra -DAGX_ARENA_WORDS=... overrides that column of csrc/agx_variants.def;
+    only: names of the kernel variants the extra flags apply to (e.g. ['FEEDING'], in either case) -- the other objects are taken from the main build's lib/obj"""
+    only = only and [o.lower() for o in only]
     OUT = out or globals()['OUT']
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     if not force and not out and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in DEPS):
         return OUT
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    base = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value'] + list(extra)
+    base = [hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value']
     if verbose:
         base.append('-Rpass-analysis=kernel-resource-usage')
     objdir = os.path.join(HERE, 'lib', 'obj' if not out else 'obj_' + os.path.splitext(os.path.basename(out))[0])
     os.makedirs(objdir, exist_ok=True)
-    jobs = [(os.path.join(objdir, 'agx_api.o'), base + ['-c', os.path.join(CSRC, 'agx_api.hip')]),
-            (os.path.join(objdir, 'agx_policy.o'), base + ['-c', os.path.join(CSRC, 'agx_policy.hip')])]      # policy step + GAE (stateless entries)
+    jobs = [(os.path.join(objdir, 'agx_api.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_api.hip')]),
+            (os.path.join(objdir, 'agx_policy.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_policy.hip')])]      # policy step + GAE (stateless entries)
     reuse = []
-    for v in VARIANTS:
-        if only and v not in only:
-            reuse.append(os.path.join(HERE, 'lib', 'obj', 'agx_kernels_%s.o' % v.lower()))
+    for v in variants.VARIANTS:
+        if only and v.name not in only:
+            reuse.append(os.path.join(HERE, 'lib', 'obj', 'agx_kernels_%s.o' % v.name))
             continue
-        jobs.append((os.path.join(objdir, 'agx_kernels_%s.o' % v.lower()), base + ['-DAGX_VARIANT_' + v, '-c', os.path.join(CSRC, 'agx_kernels.hip')]))
+        jobs.append((os.path.join(objdir, 'agx_kernels_%s.o' % v.name), base + variants.defines(v) + list(extra) + ['-c', os.path.join(CSRC, 'agx_kernels.hip')]))
     if only:
         jobs[0] = (os.path.join(HERE, 'lib', 'obj', 'agx_api.o'), None)
         jobs[1] = (os.path.join(HERE, 'lib', 'obj', 'agx_policy.o'), None)

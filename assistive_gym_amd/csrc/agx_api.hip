@@ -151,7 +151,7 @@ static void forget_warm(agx_handle_s* h, const uint8_t* mask_dev, hipStream_t st
 
 extern "C" {
 
-const char* agx_version(void) { return "libagx 0.2 (gfx950, wave-per-env stepper; variants: feeding, bed_bathing, scratch_itch, bed_settle, dressing)"; }
+const char* agx_version(void) { return "libagx 0.2 (gfx950, wave-per-env stepper)"; }
 const char* agx_last_error(void) { return g_err.c_str(); }
 int agx_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 int agx_lds_bytes_per_env(void) { return agx_variant_feeding()->lds_bytes; }
@@ -166,10 +166,12 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
     return fail(AGX_E_BLOB, "agx_create: not a model blob of this version");
   const agx_variant* V = nullptr;
   {
-    // the first (smallest) variant with the model's task layer whose limits hold the model
-    const agx_variant* all[17] = {agx_variant_feeding(), agx_variant_feeding_l(), agx_variant_feeding_m(), agx_variant_bed_bathing(), agx_variant_bed_bathing_l(), agx_variant_bed_bathing_m(),
-                                 agx_variant_scratch_itch(), agx_variant_scratch_itch_m(), agx_variant_bed_settle(),
-                                 agx_variant_dressing(), agx_variant_dressing_l(), agx_variant_dressing_m(), agx_variant_arm_manipulation(), agx_variant_arm_manipulation_l(), agx_variant_drinking(), agx_variant_drinking_l(), agx_variant_drinking_m()};
+    // the first variant, in the order of agx_variants.def, with the model's task layer whose limits hold the model
+#define AGX_VARIANT(name, ...) agx_variant_##name(),
+    const agx_variant* all[] = {
+#include "agx_variants.def"
+    };
+#undef AGX_VARIANT
     bool task_seen = false;
     for (const agx_variant* v : all) {
       if (v->task_kind != hi[AGX_H_TASK_KIND]) continue;
@@ -187,8 +189,8 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
     if (G[AGX_G_A1] - G[AGX_G_A0] > 128 || G[AGX_G_B1] - G[AGX_G_B0] > 128 || (G[AGX_G_B0F] >= 0 && G[AGX_G_B1F] - G[AGX_G_B0F] > 128))
       return fail(AGX_E_LIMIT, "agx_create: a pair group has a collider range of more than 128 colliders");
   }
-  bool can_sample = V->sample != nullptr;   // the reset generator's IK is compiled for a serial 7-DoF arm carrying the end effector
-  if (can_sample) {
+  bool can_sample = true;   // every variant carries the reset generator; what follows finds the models it cannot sample
+  {   // (scope of X and T)  Its IK is compiled for a serial 7-DoF arm carrying the end effector
     const int32_t* X = hi + hi[AGX_H_OFF_RESET];
     const int32_t* T = hi + hi[AGX_H_OFF_TASK];
     // the arm: rs_narm joints in a serial chain (AGX_X_CHAIN: each joint's parent is the one before, the first hangs off the base), the

@@ -4,8 +4,8 @@
 
 namespace agx {
 
-// A variant of the kernels is compiled per task (agx_kernels.hip is built once per variant); the limits below size
-// its LDS / register footprint.  Defaults = FeedingJaco (10 robot + 4 head DoFs, tool + bowl + 8 particles).
+// agx_kernels.hip is built once per variant, with the limits of the variant's line in agx_variants.def as -D flags; they size its LDS /
+// register footprint.  The defaults below only serve builds of these sources without a row (tests/test_sanitizers.py); an A/B build overrides a column with --extra, which build.py puts behind the row's flags.
 #ifndef AGX_MAX_DOF
 #define AGX_MAX_DOF 16
 #endif
@@ -18,7 +18,9 @@ namespace agx {
 #ifndef AGX_TASK           // AGX_TASK_* of include/agx_blob.h: the task layer compiled into the finish / observe kernels
 #define AGX_TASK 0
 #endif
-#define AGX_HAS_SAMPLER 1   // the device-side reset generator (agx_reset.h): every task (arm manipulation: the single-arm robots)
+// Always 1, and nothing in this tree tests it.  It stays for one reader: tests/emu/emu_main.cpp as it stood before the variant table guards its
+// agx_emu_sample with it, and the suite of that commit must keep running against these headers (it is how this change is compared with its parent).
+#define AGX_HAS_SAMPLER 1
 constexpr int MAX_DOF = AGX_MAX_DOF;
 constexpr int MAX_FREE = AGX_MAX_FREE;
 constexpr int MAX_BLOCK = AGX_MAX_BLOCK;

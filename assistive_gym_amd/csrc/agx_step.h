@@ -35,6 +35,4 @@
 #include "agx_water.h"
 #endif
 #include "agx_env.h"
-#if AGX_HAS_SAMPLER
 #include "agx_reset.h"
-#endif

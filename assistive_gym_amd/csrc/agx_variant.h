@@ -10,7 +10,7 @@ struct agx_variant {
   int max_dof, max_free, max_block, max_human, max_coll, st_words, max_con, max_rows;
   int lds_bytes, lds_solve_bytes, scr_words, dbg_words;
   int dbg_con, dbg_minv, dbg_hdr, dbg_lam, dbg_time, dbg_qdd;     // debug record layout (agx_debug_layout)
-  int rs_narm;                           // arm DoFs the reset generator's IK is compiled for, 0 = no reset generator in this variant
+  int rs_narm;                           // arm DoFs the reset generator's IK is compiled for
   // one-time kernel attribute set-up (dynamic LDS sizes)
   hipError_t (*init)(void);
   // launchers: grid = ne workgroups of one wavefront, environments [e0, e0 + ne)
@@ -27,7 +27,7 @@ struct agx_variant {
   void (*observe)(hipStream_t st, int n_envs, const uint32_t* blob, float* state, float* obs, int sw, int obs_dim, const uint8_t* mask);   // mask: null = every environment
   void (*sample)(hipStream_t st, int n_envs, const uint32_t* blob, float* state, unsigned long long seed0, const unsigned long long* seeds, const uint8_t* mask,
                  int impairment_mode, int gender_mode, float* info4, int* episode, int sw, const int* first_restart, int* chosen,
-                 const float* settled, int settled_sw, const float* fell);   // null without a reset generator; settled: [n_envs][settled_sw] records of the attached rag-doll model (or null); fell: [n_envs][sw] records of the attached fall model (arm manipulation, or null)
+                 const float* settled, int settled_sw, const float* fell);   // settled: [n_envs][settled_sw] records of the attached rag-doll model (or null); fell: [n_envs][sw] records of the attached fall model (arm manipulation, or null)
   // the garment (agx_cloth.h): nsub substeps replaying the trace; null in variants without a cloth
   void (*cloth)(hipStream_t st, int ne, const uint32_t* blob, const float* state, const float* trace, float* cloth, float* report, int e0, int n_envs, int sw,
                 int trace_words, int cloth_words, int report_words, int nsub, const uint8_t* active, int lds_bytes);
@@ -42,20 +42,7 @@ struct agx_variant {
   int scr_warm_word;
 };
 
-extern "C" const agx_variant* agx_variant_feeding(void);
-extern "C" const agx_variant* agx_variant_bed_bathing(void);
-extern "C" const agx_variant* agx_variant_scratch_itch(void);
-extern "C" const agx_variant* agx_variant_bed_settle(void);
-extern "C" const agx_variant* agx_variant_dressing(void);
-extern "C" const agx_variant* agx_variant_arm_manipulation(void);
-extern "C" const agx_variant* agx_variant_bed_bathing_l(void);
-extern "C" const agx_variant* agx_variant_feeding_l(void);
-extern "C" const agx_variant* agx_variant_feeding_m(void);
-extern "C" const agx_variant* agx_variant_bed_bathing_m(void);
-extern "C" const agx_variant* agx_variant_scratch_itch_m(void);
-extern "C" const agx_variant* agx_variant_dressing_m(void);
-extern "C" const agx_variant* agx_variant_dressing_l(void);
-extern "C" const agx_variant* agx_variant_arm_manipulation_l(void);
-extern "C" const agx_variant* agx_variant_drinking(void);
-extern "C" const agx_variant* agx_variant_drinking_l(void);
-extern "C" const agx_variant* agx_variant_drinking_m(void);
+// one accessor per line of agx_variants.def: agx_variant_<name>()
+#define AGX_VARIANT(name, ...) extern "C" const agx_variant* agx_variant_##name(void);
+#include "agx_variants.def"
+#undef AGX_VARIANT

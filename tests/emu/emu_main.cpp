@@ -92,7 +92,6 @@ extern "C" int agx_emu_run(const uint32_t* blob, float* state, const float* acti
   if (mode == 0 && !rc) rc = run_wave(lds, agx::LDS_WORDS, [&](int lane) { agx::env_finish(blob, state, action, scratch, obs, reward, done, info, lds, lane); });
   return rc;
 }
-#if AGX_HAS_SAMPLER
 // settled (may be null): the rag-doll model's settled state record of this environment (bed bathing, AGX_X_FLAGS bit 4)
 // fell (may be null): the fall model's record of this environment after the arm's fall (arm manipulation, AGX_X_FLAGS bit 7)
 extern "C" int agx_emu_sample(const uint32_t* blob, float* state, uint64_t seed, int impairment_mode, int gender_mode, float* info4, const float* settled, const float* fell) {
@@ -112,7 +111,6 @@ extern "C" int agx_emu_sample(const uint32_t* blob, float* state, uint64_t seed,
   }
   return rc;
 }
-#endif
 // agx_check_collisions: the build pass on the state as it is, then the flags (returns them, -1 on divergent control flow)
 extern "C" int agx_emu_check_collisions(const uint32_t* blob, float* state) {
   static float lds[agx::LDS_WORDS > agx::LDS_SOLVE_WORDS ? agx::LDS_WORDS : agx::LDS_SOLVE_WORDS];

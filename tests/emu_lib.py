@@ -5,45 +5,42 @@ import subprocess
 
 import numpy as np
 
+from assistive_gym_amd import variants
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, 'tests', 'emu')
 CSRC = os.path.join(ROOT, 'assistive_gym_amd', 'csrc')
 _LIBS = {}
-# kernel variants (limits + task layer), the same -D sets as csrc/agx_kernels.hip
-VARIANT_DEFS = {0: [], 1: ['-DAGX_MAX_DOF=20', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=10', '-DAGX_TASK=1'],
-                2: ['-DAGX_MAX_DOF=24', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=12', '-DAGX_ARENA_WORDS=4096', '-DAGX_TASK=2']}
+# emulator kinds: every kernel variant of csrc/agx_variants.def under its own name, compiled with the variant's -D flags (variants.defines: what
+# the device build of csrc/agx_kernels.hip gets), and the experimental kinds below = (base variant, extra flags); tests register more with derive()
+DERIVED = {}
 
 
-VARIANT_DEFS[3] = ['-DAGX_MAX_DOF=20', '-DAGX_MAX_FREE=1', '-DAGX_MAX_BLOCK=10', '-DAGX_TASK=3']      # dressing (rigid scene; the cloth kernel is a workgroup kernel)
-VARIANT_DEFS[4] = ['-DAGX_MAX_DOF=20', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=10', '-DAGX_TASK=4']      # arm manipulation
-VARIANT_DEFS['drinking'] = ['-DAGX_MAX_FREE=1', '-DAGX_TASK=5']      # the feeding limits, the drinking task layer, the water kernel (csrc/agx_water.h)
-VARIANT_DEFS['drinking_l'] = ['-DAGX_MAX_FREE=1', '-DAGX_MAX_BLOCK=12', '-DAGX_ARENA_WORDS=4040', '-DAGX_TASK=5']      # DrinkingPR2
-VARIANT_DEFS['drinking_m'] = ['-DAGX_MAX_FREE=1', '-DAGX_MAX_DOF=20', '-DAGX_MAX_BLOCK=16', '-DAGX_ARENA_WORDS=4040', '-DAGX_TASK=5']      # DrinkingStretch
-VARIANT_DEFS['feeding_abs_travel'] = ['-DAGX_NO_REL_TRAVEL']      # narrowphase limits from the per-collider (absolute) travel distances only
-VARIANT_DEFS['feeding_trace'] = ['-DAGX_EMU_TRACE_GJK']      # tests/diag/narrowphase_passes.py
-VARIANT_DEFS['feeding_trace_sched'] = ['-DAGX_EMU_TRACE_SCHED', '-DAGX_PGS_LV=3']      # tests/diag/solve_schedule_study.py
-VARIANT_DEFS['feeding_scan4'] = ['-DAGX_GJK_SCAN_WIDE=0', '-DAGX_GJK_SCAN_ONE=0']      # the 4-per-round support scan of rounds 3-5 (csrc/agx_gjk.h)
-VARIANT_DEFS['feeding_reg'] = ['-DAGX_PGS_LV=0']       # the register sweep of csrc/agx_pgs.h (its C++ twin) for the scenes that take a row-local sweep (csrc/agx_pgs_lvw.h, agx_pgs_lvs.h) by default
-VARIANT_DEFS['feeding_lvs'] = ['-DAGX_PGS_LV=3']       # the row-local sweep with scalar row headers (csrc/agx_pgs_lvs.h), one row per visit: the default of round 5, now the fallback of ...
-VARIANT_DEFS['feeding_lvs_cap'] = ['-DAGX_PGS_LV=3', '-DAGX_LV_WINDOW_CAP=300']       # ... with a small LDS window: most rows read their pairs from the scratch record
-VARIANT_DEFS['feeding_lvw_cap'] = ['-DAGX_LV_WINDOW_CAP=300']       # the wide row-local sweep (csrc/agx_pgs_lvw.h, the default: variant 0) with a small LDS window
-VARIANT_DEFS['feeding_lvw_8steps'] = ['-DAGX_LVW_MAX_STEPS=8']       # ... whose scheduler gives up beyond 8 steps per part: every ordinary substep falls back to the narrow sweep
-VARIANT_DEFS['feeding_l'] = ['-DAGX_MAX_COLL=320', '-DAGX_MAX_BLOCK=12', '-DAGX_ARENA_WORDS=4040']
-VARIANT_DEFS['feeding_m'] = ['-DAGX_MAX_DOF=20', '-DAGX_MAX_BLOCK=16', '-DAGX_MAX_COLL=320', '-DAGX_ST_WORDS=344', '-DAGX_ARENA_WORDS=4040']    # FeedingStretch
-VARIANT_DEFS['bed_m'] = ['-DAGX_MAX_DOF=28', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=16', '-DAGX_ARENA_WORDS=5632', '-DAGX_TASK=1']          # BedBathingStretch
-VARIANT_DEFS['scratch_m'] = ['-DAGX_MAX_DOF=28', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=16', '-DAGX_ARENA_WORDS=5632', '-DAGX_TASK=2']      # ScratchItchStretch
-VARIANT_DEFS['dressing_m'] = ['-DAGX_MAX_DOF=28', '-DAGX_MAX_FREE=1', '-DAGX_MAX_BLOCK=16', '-DAGX_ARENA_WORDS=5632', '-DAGX_TASK=3']     # DressingStretch (rigid scene)
-VARIANT_DEFS['dressing_l'] = ['-DAGX_MAX_DOF=24', '-DAGX_MAX_FREE=1', '-DAGX_MAX_BLOCK=12', '-DAGX_ARENA_WORDS=4096', '-DAGX_TASK=3']
-VARIANT_DEFS['arm_l'] = ['-DAGX_MAX_DOF=32', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=22', '-DAGX_ARENA_WORDS=7552', '-DAGX_TASK=4']
-VARIANT_DEFS['bed_l'] = ['-DAGX_MAX_DOF=24', '-DAGX_MAX_FREE=2', '-DAGX_MAX_BLOCK=12', '-DAGX_ARENA_WORDS=4096', '-DAGX_TASK=1']
-VARIANT_DEFS['settle'] = ['-DAGX_MAX_DOF=48', '-DAGX_MAX_FREE=1', '-DAGX_MAX_BLOCK=48', '-DAGX_ARENA_WORDS=11968', '-DAGX_SCR_ENT=16384', '-DAGX_TASK=1']
+def derive(kind, base, flags):
+    DERIVED.setdefault(kind, (base, list(flags)))
 
 
-def lib(task_kind=0):
-    if task_kind not in _LIBS:
-        so = os.path.join(EMU, 'libagx_emu_%s.so' % task_kind)
+def kind_defs(kind):
+    base, flags = DERIVED.get(kind, (kind, []))
+    return variants.defines(next(v for v in variants.VARIANTS if v.name == base)) + flags
+
+
+derive('feeding_abs_travel', 'feeding', ['-DAGX_NO_REL_TRAVEL'])      # narrowphase limits from the per-collider (absolute) travel distances only
+derive('feeding_trace', 'feeding', ['-DAGX_EMU_TRACE_GJK'])      # tests/diag/narrowphase_passes.py
+derive('feeding_trace_sched', 'feeding', ['-DAGX_EMU_TRACE_SCHED', '-DAGX_PGS_LV=3'])      # tests/diag/solve_schedule_study.py
+derive('feeding_scan4', 'feeding', ['-DAGX_GJK_SCAN_WIDE=0', '-DAGX_GJK_SCAN_ONE=0'])      # the 4-per-round support scan of rounds 3-5 (csrc/agx_gjk.h)
+derive('feeding_reg', 'feeding', ['-DAGX_PGS_LV=0'])       # the register sweep of csrc/agx_pgs.h (its C++ twin) for the scenes that take a row-local sweep (csrc/agx_pgs_lvw.h, agx_pgs_lvs.h) by default
+derive('feeding_lvs', 'feeding', ['-DAGX_PGS_LV=3'])       # the row-local sweep with scalar row headers (csrc/agx_pgs_lvs.h), one row per visit: the default of round 5, now the fallback of ...
+derive('feeding_lvs_cap', 'feeding', ['-DAGX_PGS_LV=3', '-DAGX_LV_WINDOW_CAP=300'])       # ... with a small LDS window: most rows read their pairs from the scratch record
+derive('feeding_lvw_cap', 'feeding', ['-DAGX_LV_WINDOW_CAP=300'])       # the wide row-local sweep (csrc/agx_pgs_lvw.h, the default of the feeding variant) with a small LDS window
+derive('feeding_lvw_8steps', 'feeding', ['-DAGX_LVW_MAX_STEPS=8'])       # ... whose scheduler gives up beyond 8 steps per part: every ordinary substep falls back to the narrow sweep
+
+
+def lib(kind='feeding'):
+    if kind not in _LIBS:
+        so = os.path.join(EMU, 'libagx_emu_%s.so' % kind)
         deps = [os.path.join(EMU, f) for f in ('emu_main.cpp', 'agx_wave.h')] + \
-               [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.h')] + [os.path.join(ROOT, 'include', 'agx_blob.h')]
+               [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(('.h', '.def'))] + [os.path.join(ROOT, 'include', 'agx_blob.h')]
         def stale():
             return not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps)
         if stale():
@@ -52,13 +49,13 @@ def lib(task_kind=0):
                 fcntl.flock(lock, fcntl.LOCK_EX)
                 if stale():
                     tmp = '%s.%d.tmp' % (so, os.getpid())
-                    subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-I' + EMU, '-I' + CSRC] + VARIANT_DEFS[task_kind] +
+                    subprocess.check_call(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-I' + EMU, '-I' + CSRC] + kind_defs(kind) +
                                           ['-o', tmp, os.path.join(EMU, 'emu_main.cpp')])
                     os.replace(tmp, so)
         L = C.CDLL(so)
         L.agx_emu_run.restype = C.c_int
-        _LIBS[task_kind] = L
-    return _LIBS[task_kind]
+        _LIBS[kind] = L
+    return _LIBS[kind]
 
 
 def _p(a):
@@ -68,7 +65,7 @@ def _p(a):
 class Emu:
     def __init__(self, blob, kind=None):
         self.blob = blob
-        self.L = lib(kind) if kind is not None else lib('drinking_m' if blob.ndof > 16 else 'drinking_l' if blob.nrobot > 10 else 'drinking') if blob.task_kind == 5 else lib('settle' if blob.ndof > 32 else 'arm_l' if (blob.task_kind == 4 and blob.ndof > 20) else 'feeding_m' if (blob.task_kind == 0 and blob.ndof > 16) else 'feeding_l' if (blob.task_kind == 0 and blob.h['NCOLL'] > 256) else ('bed_m' if blob.task_kind == 1 and blob.nrobot > 12 else 'scratch_m' if blob.task_kind == 2 and blob.nrobot > 12 else 'bed_l' if blob.task_kind == 1 and (blob.ndof > 20 or blob.nrobot > 10) else 'dressing_m' if blob.task_kind == 3 and blob.nrobot > 12 else 'dressing_l' if blob.task_kind == 3 and (blob.ndof > 20 or blob.nrobot > 10) else blob.task_kind))
+        self.L = lib(kind if kind is not None else variants.pick(blob).name)      # as agx_create picks
         self.words = np.ascontiguousarray(blob.words)
         lay = (C.c_int * 8)()
         self.L.agx_emu_debug_layout(lay)

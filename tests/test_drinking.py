@@ -164,7 +164,7 @@ def _water_on_emulator(b, o, s, w, action):
     trace from the same start.  Returns (oracle water, kernel water, kernel report, oracle state after, info)"""
     import ctypes as C
     from emu_lib import lib, _p
-    L = lib(0)
+    L = lib('feeding')
     nsub = int(b.param('FRAME_SKIP')) * b.h['SIM_SUBSTEPS']
     trace = np.zeros((nsub, b.ndof + b.nfree, 12), np.float32)
     s0, w_o = s.copy(), w.copy()

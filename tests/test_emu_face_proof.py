@@ -17,9 +17,9 @@ import emu_lib
 from assistive_gym_amd.blob import ModelBlob
 from assistive_gym_amd.host.reset import make_states
 
-emu_lib.VARIANT_DEFS.setdefault('feeding_face_plain', ['-DAGX_FACE_PLAIN'])
-emu_lib.VARIANT_DEFS.setdefault('feeding_trace_face_plain', ['-DAGX_EMU_TRACE_GJK', '-DAGX_FACE_PLAIN'])
-NEW, PLAIN, NEW_T, PLAIN_T = 0, 'feeding_face_plain', 'feeding_trace', 'feeding_trace_face_plain'
+emu_lib.derive('feeding_face_plain', 'feeding', ['-DAGX_FACE_PLAIN'])
+emu_lib.derive('feeding_trace_face_plain', 'feeding', ['-DAGX_EMU_TRACE_GJK', '-DAGX_FACE_PLAIN'])
+NEW, PLAIN, NEW_T, PLAIN_T = 'feeding', 'feeding_face_plain', 'feeding_trace', 'feeding_trace_face_plain'
 N_STATES, N_STEPS = 6, 30
 BOWL = 1                       # free body 1 of the feeding scene: the bowl (about 100 hull pieces), resting on the table top
 FAR_MARGIN_UM = 100            # GJK_FAR_MARGIN: the traced limit is lim + radii + this
@@ -265,7 +265,7 @@ def test_other_models_bit_identical(name, module, coop):
     made = importlib.import_module('assistive_gym_amd.host.' + module).make_states(b, 1, seed=7001)
     new = emu_lib.Emu(b)
     key = [k for k, v in emu_lib._LIBS.items() if v is new.L][0]
-    emu_lib.VARIANT_DEFS.setdefault('face_plain_%s' % key, list(emu_lib.VARIANT_DEFS[key]) + ['-DAGX_FACE_PLAIN'])
+    emu_lib.derive('face_plain_%s' % key, key, ['-DAGX_FACE_PLAIN'])
     old = emu_lib.Emu(b, kind='face_plain_%s' % key)
     water = module == 'reset_drinking'
     s = [made[0][0].copy(), made[0][0].copy()]

@@ -13,10 +13,10 @@ import pytest
 import emu_lib
 from assistive_gym_amd.host.reset import make_states
 
-emu_lib.VARIANT_DEFS.setdefault('feeding_finish_gjk', ['-DAGX_FINISH_SPILL_GJK'])
-emu_lib.VARIANT_DEFS.setdefault('feeding_trace_finish_gjk', ['-DAGX_EMU_TRACE_GJK', '-DAGX_FINISH_SPILL_GJK'])
-BUILDS = (0, 'feeding_finish_gjk')              # the default (shortcut) and the switch
-TRACED = {0: 'feeding_trace', 'feeding_finish_gjk': 'feeding_trace_finish_gjk'}
+emu_lib.derive('feeding_finish_gjk', 'feeding', ['-DAGX_FINISH_SPILL_GJK'])
+emu_lib.derive('feeding_trace_finish_gjk', 'feeding', ['-DAGX_EMU_TRACE_GJK', '-DAGX_FINISH_SPILL_GJK'])
+BUILDS = ('feeding', 'feeding_finish_gjk')              # the default (shortcut) and the switch
+TRACED = {'feeding': 'feeding_trace', 'feeding_finish_gjk': 'feeding_trace_finish_gjk'}
 N_STATES, N_STEPS = 6, 30
 FAR_MARGIN_UM = 100                             # GJK_FAR_MARGIN (csrc/agx_collide.h): the traced limit is SPILL_DIST + radii + this
 
@@ -74,7 +74,7 @@ def finish_trace(e, state, action):
 def _both(blob, emus, state, what):
     """one zero-action step of `state` through the default build and the switch build: the same bits; -> the new record"""
     a = np.zeros(blob.act_dim, dtype=np.float32)
-    ref, s1 = _step(emus[0], state, a)
+    ref, s1 = _step(emus['feeding'], state, a)
     _same(ref, _step(emus['feeding_finish_gjk'], state, a)[0], what)
     return ref, blob.view(s1)
 
@@ -127,10 +127,10 @@ def test_rollouts_bit_identical(blob, emus, settled):
     pool = ThreadPoolExecutor(2)                  # the two builds are two libraries with their own emulator state: they step side by side
     for i in range(N_STATES):
         sa, sb = settled[i].copy(), settled[i].copy()
-        emus[0].forget_warm(); emus['feeding_finish_gjk'].forget_warm()
+        emus['feeding'].forget_warm(); emus['feeding_finish_gjk'].forget_warm()
         for k in range(N_STEPS):
             a = (rng.uniform(-1, 1, blob.act_dim) * (3.0 if k % 3 == 2 else 1.0)).astype(np.float32)
-            fa, fb = pool.submit(emus[0].step, sa, a), pool.submit(emus['feeding_finish_gjk'].step, sb, a)
+            fa, fb = pool.submit(emus['feeding'].step, sa, a), pool.submit(emus['feeding_finish_gjk'].step, sb, a)
             oa, ob = fa.result(), fb.result()
             what = 'state %d step %d' % (i, k)
             assert np.array_equal(oa[0].view(np.uint32), ob[0].view(np.uint32)), what + ': observation'

@@ -11,7 +11,7 @@ import pytest
 @pytest.fixture(scope='module')
 def sched():
     from emu_lib import lib
-    L = lib(0)
+    L = lib('feeding')
     L.agx_emu_lvw_schedule.restype = C.c_int
     dummy = L.agx_emu_lvw_dummy_row()
 

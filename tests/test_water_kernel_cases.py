@@ -118,7 +118,7 @@ def test_kernel_source_on_the_emulator(cases, name):
     """csrc/agx_water.h as the device compiles it, run lane by lane on the CPU (tests/emu) over the oracle's trace of each stored determined
     substep: the same judge, the same limits as tests/test_gpu_water_kernel.py"""
     from emu_lib import lib, _p
-    E = lib(0)
+    E = lib('feeding')
     blob, o = _oracle(cases, name)
     words = np.ascontiguousarray(blob.words)
     nsub = cases[name + '/recipe']['nsub']
