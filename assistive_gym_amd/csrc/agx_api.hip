@@ -111,26 +111,21 @@ extern "C" __global__ void __launch_bounds__(64) agx_selftest_kernel(float* out_
 
 struct agx_handle_s {
   const agx_variant* V;   // the compiled kernel variant serving this model
-  int* overflow_dev;      // contacts dropped by a budget since creation (all envs)
+  // what every launch passes: the model blob, the state / scratch records, their strides (agx_variant.h); with a cloth section (DressingBaxter) the
+  // garments [n_envs][2][NN][3], the link frames of every substep of an env step for the cloth kernel and its report to the finish kernel
+  agx_launch L;
+  decltype(agx_variant::build) step_build;   // the build launcher of the step path: the one with the manifold stage where the blob has AGX_P_MANIFOLD > 0
   int collision_tries;    // reset generator: successful IK restarts that may be rejected for a collision (AGX_X_COLLISION_TRIES)
-  int *first_restart_dev, *chosen_dev; uint8_t* work_dev;   // reset generator: per-env retry bookkeeping
+  int* first_restart_dev; uint8_t* work_dev;   // reset generator: per-env retry bookkeeping
   long long env_offset;   // global index of env 0 of this handle (multi-GPU sharding), see agx_set_env_offset
-  int device, n_envs, act_dim, obs_dim, sw;
+  int device;
   int iter_word;          // index of AGX_E_ITERATION in a state record (agx_reset_done_at)
-  uint32_t* blob_dev;
-  float* state_dev;
-  float* scratch_dev;   // [n_envs][SCR_WORDS]: rows, predicted velocities, contacts handed between the kernels
-  int* episode_dev;
   int frame_skip;
   int sim_sub;          // internal substeps per p.stepSimulation() (AGX_H_SIM_SUBSTEPS)
-  // models with a cloth section (DressingBaxter): garments [n_envs][2][NN][3], the link frames of every substep of an env step for the
-  // cloth kernel, its report to the finish kernel, and the garments of the reset pool (agx_set_cloth_pool)
-  int cloth_nn, cloth_words, trace_words, report_words, cloth_lds;
+  int cloth_nn;
   bool particles;       // the "cloth" section holds the water particles of the drinking scene (AGX_CL_PARTICLES), not a garment
-  float *cloth_dev, *trace_dev, *report_dev; const float* cloth_pool_dev;
+  const float* cloth_pool_dev;   // the garments of the reset pool (agx_set_cloth_pool)
   bool can_sample;      // the variant has a reset generator (agx_reset.h) and the blob fits it
-  bool manifold;        // AGX_P_MANIFOLD > 0 in the blob: the step path launches the variant's build kernel with the manifold stage
-  const uint8_t* active;// per-env mask honoured by the build / solve launches (agx_reset's masked settle), normally null
   // staging for the *_host convenience calls
   float *act_dev, *obs_dev, *rew_dev, *info_dev; uint8_t* done_dev;
   hipEvent_t ev0, ev1;
@@ -146,7 +141,7 @@ struct agx_handle_s {
 };
 
 static void forget_warm(agx_handle_s* h, const uint8_t* mask_dev, hipStream_t st) {
-  hipLaunchKernelGGL(agx_forget_warm_kernel, dim3((h->n_envs + 255) / 256), dim3(256), 0, st, h->scratch_dev, h->V->scr_words, h->V->scr_warm_word, mask_dev, h->n_envs);
+  hipLaunchKernelGGL(agx_forget_warm_kernel, dim3((h->L.n_envs + 255) / 256), dim3(256), 0, st, h->L.scratch, h->V->scr_words, h->V->scr_warm_word, mask_dev, h->L.n_envs);
 }
 
 extern "C" {
@@ -224,8 +219,9 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
   agx_handle h = new agx_handle_s();
   memset(h, 0, sizeof *h);
   h->can_sample = can_sample; h->V = V;
-  h->manifold = ((const float*)blob)[hi[AGX_H_OFF_PARAMS] + AGX_P_MANIFOLD] > 0.f;
-  if (h->manifold && !V->build_mf) { delete h; return fail(AGX_E_LIMIT, "agx_create: AGX_P_MANIFOLD is set, but this kernel variant is compiled without the manifold stage (feeding, bed_bathing, scratch_itch, arm_manipulation have it)"); }
+  const bool manifold = ((const float*)blob)[hi[AGX_H_OFF_PARAMS] + AGX_P_MANIFOLD] > 0.f;
+  h->step_build = manifold ? V->build_mf : V->build;
+  if (manifold && !V->build_mf) { delete h; return fail(AGX_E_LIMIT, "agx_create: AGX_P_MANIFOLD is set, but this kernel variant is compiled without the manifold stage (feeding, bed_bathing, scratch_itch, arm_manipulation have it)"); }
   h->settle = nullptr; h->settle_substeps = 0;
   h->reset_flags = (hi[AGX_H_OFF_TARGETS] - hi[AGX_H_OFF_RESET] >= AGX_X_COUNT || hi[AGX_H_NWORDS] - hi[AGX_H_OFF_RESET] >= AGX_X_COUNT) ? hi[hi[AGX_H_OFF_RESET] + AGX_X_FLAGS] : 0;
   const int rc = create_fill(h, blob, blob_bytes, n_envs, device);
@@ -238,41 +234,41 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
 static int create_fill(agx_handle h, const void* blob, size_t blob_bytes, int n_envs, int device) {
   const int32_t* hi = (const int32_t*)blob; const agx_variant* V = h->V; const bool can_sample = h->can_sample;
   h->iter_word = hi[AGX_H_S_ENV] + AGX_E_ITERATION;
-  h->device = device; h->n_envs = n_envs; h->act_dim = hi[AGX_H_ACT_DIM]; h->obs_dim = hi[AGX_H_OBS_DIM]; h->sw = hi[AGX_H_STATE_WORDS];
-  HIPCHK(hipMalloc(&h->blob_dev, blob_bytes));
-  HIPCHK(hipMemcpy(h->blob_dev, blob, blob_bytes, hipMemcpyHostToDevice));
-  HIPCHK(hipMalloc(&h->state_dev, (size_t)n_envs * h->sw * 4));
-  HIPCHK(hipMemset(h->state_dev, 0, (size_t)n_envs * h->sw * 4));
-  HIPCHK(hipMalloc(&h->scratch_dev, (size_t)n_envs * V->scr_words * 4));
-  HIPCHK(hipMemset(h->scratch_dev, 0, (size_t)n_envs * V->scr_words * 4));
-  HIPCHK(hipMalloc(&h->overflow_dev, 4));
-  HIPCHK(hipMemset(h->overflow_dev, 0, 4));
+  h->device = device; h->L.n_envs = n_envs; h->L.act_dim = hi[AGX_H_ACT_DIM]; h->L.obs_dim = hi[AGX_H_OBS_DIM]; h->L.sw = hi[AGX_H_STATE_WORDS];
+  HIPCHK(hipMalloc(&h->L.blob, blob_bytes));
+  HIPCHK(hipMemcpy(h->L.blob, blob, blob_bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&h->L.state, (size_t)n_envs * h->L.sw * 4));
+  HIPCHK(hipMemset(h->L.state, 0, (size_t)n_envs * h->L.sw * 4));
+  HIPCHK(hipMalloc(&h->L.scratch, (size_t)n_envs * V->scr_words * 4));
+  HIPCHK(hipMemset(h->L.scratch, 0, (size_t)n_envs * V->scr_words * 4));
+  HIPCHK(hipMalloc(&h->L.overflow, 4));
+  HIPCHK(hipMemset(h->L.overflow, 0, 4));
   h->collision_tries = can_sample ? hi[hi[AGX_H_OFF_RESET] + AGX_X_COLLISION_TRIES] : 0;
-  HIPCHK(hipMalloc(&h->first_restart_dev, (size_t)n_envs * 4)); HIPCHK(hipMalloc(&h->chosen_dev, (size_t)n_envs * 4)); HIPCHK(hipMalloc(&h->work_dev, (size_t)n_envs));
+  HIPCHK(hipMalloc(&h->first_restart_dev, (size_t)n_envs * 4)); HIPCHK(hipMalloc(&h->L.chosen, (size_t)n_envs * 4)); HIPCHK(hipMalloc(&h->work_dev, (size_t)n_envs));
   h->frame_skip = (int)((const float*)blob)[hi[AGX_H_OFF_PARAMS] + AGX_P_FRAME_SKIP];
   h->sim_sub = hi[AGX_H_SIM_SUBSTEPS] > 1 ? hi[AGX_H_SIM_SUBSTEPS] : 1;
   if (hi[AGX_H_OFF_CLOTH]) {
     if (!V->cloth || !V->cloth_lds_bytes) return fail(AGX_E_LIMIT, "agx_create: the model has a cloth but the kernel variant of its task has no cloth kernel");
     const int32_t* cl = hi + hi[AGX_H_OFF_CLOTH];
     h->cloth_nn = cl[AGX_CL_NN];
-    h->cloth_words = 6 * h->cloth_nn; h->report_words = AGX_CLOTH_REPORT_WORDS(h->cloth_nn) + AGX_CLOTH_SCRATCH_WORDS(h->cloth_nn);
-    h->trace_words = h->frame_skip * h->sim_sub * (hi[AGX_H_NDOF] + hi[AGX_H_NFREE]) * 12;      // per substep: the frames of the moving links, then of the free bodies
-    h->cloth_lds = V->cloth_lds_bytes(h->cloth_nn);          // agxc::lds_words of the variant's own cloth kernel
+    h->L.cloth_words = 6 * h->cloth_nn; h->L.report_words = AGX_CLOTH_REPORT_WORDS(h->cloth_nn) + AGX_CLOTH_SCRATCH_WORDS(h->cloth_nn);
+    h->L.trace_words = h->frame_skip * h->sim_sub * (hi[AGX_H_NDOF] + hi[AGX_H_NFREE]) * 12;      // per substep: the frames of the moving links, then of the free bodies
+    h->L.cloth_lds = V->cloth_lds_bytes(h->cloth_nn);          // agxc::lds_words of the variant's own cloth kernel
     h->particles = cl[AGX_CL_PARTICLES] != 0;
     if (cl[AGX_CL_PARTICLES]) {      // the water of the drinking scene (agx_water.h): one wavefront, lane = particle; report = one word per particle
-      h->report_words = 64;
+      h->L.report_words = 64;
       if (h->cloth_nn > 64 || cl[AGX_CL_NSHAPE] > 192 || hi[AGX_H_NDOF] + hi[AGX_H_NHUMAN] + hi[AGX_H_NFREE] + 2 > 64 || hi[AGX_H_TASK_KIND] != AGX_TASK_DRINKING)
         return fail(AGX_E_LIMIT, "agx_create: particles exceed the limits of the water kernel");
-    } else if (h->cloth_lds > 160 * 1024 || h->cloth_nn > 4096 || cl[AGX_CL_NCOLOR] - (AGX_CLOTH_THREADS / 64) * cl[AGX_CL_NPATCH_COLOR] > AGX_CLOTH_MAX_COLORS || cl[AGX_CL_NPATCH_COLOR] < 0 || cl[AGX_CL_MAX_LINKS_PER_COLOR] > 1024 ||
+    } else if (h->L.cloth_lds > 160 * 1024 || h->cloth_nn > 4096 || cl[AGX_CL_NCOLOR] - (AGX_CLOTH_THREADS / 64) * cl[AGX_CL_NPATCH_COLOR] > AGX_CLOTH_MAX_COLORS || cl[AGX_CL_NPATCH_COLOR] < 0 || cl[AGX_CL_MAX_LINKS_PER_COLOR] > 1024 ||
         cl[AGX_CL_NSHAPE] > 192 || hi[AGX_H_NDOF] + hi[AGX_H_NHUMAN] + 2 > 64 || cl[AGX_CL_NN] > 65535 || hi[AGX_H_NFREE] != 0) return fail(AGX_E_LIMIT, "agx_create: cloth exceeds the limits of the cloth kernel");
-    HIPCHK(hipMalloc(&h->cloth_dev, (size_t)n_envs * h->cloth_words * 4)); HIPCHK(hipMemset(h->cloth_dev, 0, (size_t)n_envs * h->cloth_words * 4));
-    HIPCHK(hipMalloc(&h->trace_dev, (size_t)n_envs * h->trace_words * 4)); HIPCHK(hipMemset(h->trace_dev, 0, (size_t)n_envs * h->trace_words * 4));
-    HIPCHK(hipMalloc(&h->report_dev, (size_t)n_envs * h->report_words * 4)); HIPCHK(hipMemset(h->report_dev, 0, (size_t)n_envs * h->report_words * 4));
+    HIPCHK(hipMalloc(&h->L.cloth, (size_t)n_envs * h->L.cloth_words * 4)); HIPCHK(hipMemset(h->L.cloth, 0, (size_t)n_envs * h->L.cloth_words * 4));
+    HIPCHK(hipMalloc(&h->L.trace, (size_t)n_envs * h->L.trace_words * 4)); HIPCHK(hipMemset(h->L.trace, 0, (size_t)n_envs * h->L.trace_words * 4));
+    HIPCHK(hipMalloc(&h->L.report, (size_t)n_envs * h->L.report_words * 4)); HIPCHK(hipMemset(h->L.report, 0, (size_t)n_envs * h->L.report_words * 4));
   }
-  HIPCHK(hipMalloc(&h->episode_dev, (size_t)n_envs * 4));
-  HIPCHK(hipMemset(h->episode_dev, 0, (size_t)n_envs * 4));
-  HIPCHK(hipMalloc(&h->act_dev, (size_t)n_envs * h->act_dim * 4));
-  HIPCHK(hipMalloc(&h->obs_dev, (size_t)n_envs * h->obs_dim * 4));
+  HIPCHK(hipMalloc(&h->L.episode, (size_t)n_envs * 4));
+  HIPCHK(hipMemset(h->L.episode, 0, (size_t)n_envs * 4));
+  HIPCHK(hipMalloc(&h->act_dev, (size_t)n_envs * h->L.act_dim * 4));
+  HIPCHK(hipMalloc(&h->obs_dev, (size_t)n_envs * h->L.obs_dim * 4));
   HIPCHK(hipMalloc(&h->rew_dev, (size_t)n_envs * 4));
   HIPCHK(hipMalloc(&h->info_dev, (size_t)n_envs * AGX_INFO_DIM * 4));
   HIPCHK(hipMalloc(&h->done_dev, (size_t)n_envs));
@@ -296,9 +292,9 @@ static int create_fill(agx_handle h, const void* blob, size_t blob_bytes, int n_
 void agx_destroy(agx_handle h) {
   if (!h) return;
   hipSetDevice(h->device);
-  hipFree(h->scratch_dev); hipFree(h->overflow_dev); hipFree(h->first_restart_dev); hipFree(h->chosen_dev); hipFree(h->work_dev); hipFree(h->blob_dev); hipFree(h->state_dev); hipFree(h->episode_dev); hipFree(h->act_dev); hipFree(h->obs_dev);
+  hipFree(h->L.scratch); hipFree(h->L.overflow); hipFree(h->first_restart_dev); hipFree(h->L.chosen); hipFree(h->work_dev); hipFree(h->L.blob); hipFree(h->L.state); hipFree(h->L.episode); hipFree(h->act_dev); hipFree(h->obs_dev);
   hipFree(h->rew_dev); hipFree(h->info_dev); hipFree(h->done_dev);
-  if (h->cloth_dev) { hipFree(h->cloth_dev); hipFree(h->trace_dev); hipFree(h->report_dev); }
+  if (h->L.cloth) { hipFree(h->L.cloth); hipFree(h->L.trace); hipFree(h->L.report); }
   if (h->ev0) hipEventDestroy(h->ev0); if (h->ev1) hipEventDestroy(h->ev1);      // a handle whose creation failed half way holds nulls
   for (int c = 0; c < 8; c++) for (int k = 0; k < 16; k++) if (h->kev[c][k]) hipEventDestroy(h->kev[c][k]);
   if (h->fork_ev) hipEventDestroy(h->fork_ev);
@@ -308,132 +304,109 @@ void agx_destroy(agx_handle h) {
 
 int agx_dims(agx_handle h, int* n_envs, int* act_dim, int* obs_dim, int* state_words) {
   if (!h) return fail(AGX_E_ARG, "agx_dims: null handle");
-  if (n_envs) *n_envs = h->n_envs; if (act_dim) *act_dim = h->act_dim; if (obs_dim) *obs_dim = h->obs_dim; if (state_words) *state_words = h->sw;
+  if (n_envs) *n_envs = h->L.n_envs; if (act_dim) *act_dim = h->L.act_dim; if (obs_dim) *obs_dim = h->L.obs_dim; if (state_words) *state_words = h->L.sw;
   return AGX_OK;
 }
 
 int agx_set_state(agx_handle h, const float* host_states) {
   if (!h || !host_states) return fail(AGX_E_ARG, "agx_set_state: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(h->state_dev, host_states, (size_t)h->n_envs * h->sw * 4, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(h->episode_dev, 0, (size_t)h->n_envs * 4));
+  HIPCHK(hipMemcpy(h->L.state, host_states, (size_t)h->L.n_envs * h->L.sw * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(h->L.episode, 0, (size_t)h->L.n_envs * 4));
   forget_warm(h, nullptr, nullptr); HIPCHK(hipGetLastError()); HIPCHK(hipDeviceSynchronize());
   return AGX_OK;
 }
 int agx_get_state(agx_handle h, float* host_states) {
   if (!h || !host_states) return fail(AGX_E_ARG, "agx_get_state: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(host_states, h->state_dev, (size_t)h->n_envs * h->sw * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host_states, h->L.state, (size_t)h->L.n_envs * h->L.sw * 4, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
-int agx_state_dev(agx_handle h, float** out_dev) { if (!h || !out_dev) return fail(AGX_E_ARG, "agx_state_dev: bad argument"); *out_dev = h->state_dev; return AGX_OK; }
+int agx_state_dev(agx_handle h, float** out_dev) { if (!h || !out_dev) return fail(AGX_E_ARG, "agx_state_dev: bad argument"); *out_dev = h->L.state; return AGX_OK; }
 
-// one p.stepSimulation() for the environments [e0, e0+ne): build + solve
-static int launch_substep(agx_handle h, const float* act, float* dbg, int e0, int ne, hipStream_t st, int phase, bool settle) {
-  (h->manifold ? h->V->build_mf : h->V->build)(st, ne, h->blob_dev, h->state_dev, act, h->scratch_dev, dbg, e0, h->n_envs, h->sw, h->act_dim, h->active, h->overflow_dev, h->trace_dev, h->trace_words, phase);
-  HIPCHK(hipGetLastError());
-  const int ph = settle ? (phase | AGX_PHASE_SETTLE) : phase;
-  // the packed kernel (four environments per wavefront) where the variant has one; the debug path keeps the single-environment kernel
-  // (its per-phase cycle counters); AGX_SOLVE=old selects it for same-box A/B runs
-  h->V->solve(st, ne, h->blob_dev, h->state_dev, h->scratch_dev, dbg, e0, h->n_envs, h->sw, h->active, ph);
-  HIPCHK(hipGetLastError());
-  return AGX_OK;
-}
-// fork the caller's stream into the chunk streams, run `n_substeps` (and optionally the finish
-// kernel) per chunk, join back.  Work of one chunk is ordered; chunks are independent.
-static int launch_chunked(agx_handle h, int n_substeps, const float* act, float* obs, float* rew, uint8_t* done, float* info, float* dbg, bool finish, void* stream) {
+// what an env step reads and writes beyond the handle's own buffers (device pointers, [n_envs] rows each)
+struct step_io { const float* act; float *obs, *rew; uint8_t* done; float* info; };
+// agx_step_timed: the events of one launch_chunked, per chunk -- one before the first launch, one after every launch
+struct launch_recorder { hipEvent_t (*ev)[16]; int n[8]; };
+// The one launch sequence.  Fork the caller's stream into the chunk streams, run `n_substeps` p.stepSimulation() calls per chunk -- each
+// sim_sub times [build, solve] -- and, for an env step (io given), the finish kernel; join back.  Work of one chunk is ordered; chunks are
+// independent.  Without io it is a settle, and the solve kernel's phase says so.  dbg: debug records of the first substep, or null.
+// active: per-env mask honoured by the build / solve / cloth launches (agx_reset's masked settle), null = every environment
+static int launch_chunked(agx_handle h, int n_substeps, const step_io* io, float* dbg, const uint8_t* active, void* stream, launch_recorder* rec) {
   HIPCHK(hipSetDevice(h->device));
+  const agx_launch& L = h->L; const agx_variant* V = h->V;
   hipStream_t user = (hipStream_t)stream;
-  const int nc = h->n_chunks, per = (h->n_envs + nc - 1) / nc;
+  const int nc = h->n_chunks, per = (L.n_envs + nc - 1) / nc;
   HIPCHK(hipEventRecord(h->fork_ev, user));
   for (int c = 0; c < nc; c++) {
-    const int e0 = c * per, ne = (e0 + per <= h->n_envs ? per : h->n_envs - e0);
+    const int e0 = c * per, ne = (e0 + per <= L.n_envs ? per : L.n_envs - e0);
     if (ne <= 0) continue;
     hipStream_t st = nc == 1 ? user : h->cs[c];
     if (nc > 1) HIPCHK(hipStreamWaitEvent(st, h->fork_ev, 0));
+    auto mark = [&]() { return rec ? hipEventRecord(rec->ev[c][rec->n[c]++], st) : hipSuccess; };
+    auto launched = [&]() { const hipError_t e = hipGetLastError(); return e != hipSuccess ? e : mark(); };
+    HIPCHK(mark());
     // n_substeps counts p.stepSimulation() calls, each sim_sub internal substeps long.  With a cloth, the rigid substeps of up to frame_skip
     // calls run first (leaving their link frames in the trace), then one cloth launch replays them (one-way coupling, agx_cloth.h).
     for (int g0 = 0; g0 < n_substeps; g0 += h->frame_skip) {
       const int gs = n_substeps - g0 < h->frame_skip ? n_substeps - g0 : h->frame_skip, nsub = gs * h->sim_sub;
-      for (int k = 0; k < nsub; k++) { const bool first = g0 == 0 && k == 0; int rc = launch_substep(h, first ? act : nullptr, first ? dbg : nullptr, e0, ne, st, k, !finish); if (rc) return rc; }
-      if (h->cloth_dev) {
-        h->V->cloth(st, ne, h->blob_dev, h->state_dev, h->trace_dev, h->cloth_dev, h->report_dev, e0, h->n_envs, h->sw, h->trace_words, h->cloth_words, h->report_words, nsub,
-                    h->active, h->cloth_lds);
-        HIPCHK(hipGetLastError());
+      for (int k = 0; k < nsub; k++) {
+        const bool first = g0 == 0 && k == 0;
+        h->step_build(L, st, e0, ne, first && io ? io->act : nullptr, first ? dbg : nullptr, active, k, true);
+        HIPCHK(launched());
+        V->solve(L, st, e0, ne, first ? dbg : nullptr, active, io ? k : (k | AGX_PHASE_SETTLE));
+        HIPCHK(launched());
       }
+      if (L.cloth) { V->cloth(L, st, e0, ne, nsub, active); HIPCHK(launched()); }
     }
-    if (finish) {
-      h->V->finish(st, ne, h->blob_dev, h->state_dev, act, h->scratch_dev, obs, rew, done, info, e0, h->n_envs, h->sw, h->act_dim, h->obs_dim, h->report_dev, h->report_words,
-                   h->cloth_dev, h->cloth_words);
-      HIPCHK(hipGetLastError());
-    }
+    if (io) { V->finish(L, st, e0, ne, io->act, io->obs, io->rew, io->done, io->info); HIPCHK(launched()); }
     if (nc > 1) { HIPCHK(hipEventRecord(h->join_ev[c], st)); HIPCHK(hipStreamWaitEvent(user, h->join_ev[c], 0)); }
   }
   return AGX_OK;
 }
-static int launch_step(agx_handle h, const float* act, float* obs, float* rew, uint8_t* done, float* info, float* dbg, void* stream) {
-  return launch_chunked(h, h->frame_skip, act, obs, rew, done, info, dbg, true, stream);
-}
 int agx_settle(agx_handle h, int n_substeps, void* stream) {
   if (!h || n_substeps < 0) return fail(AGX_E_ARG, "agx_settle: bad argument");
-  return launch_chunked(h, n_substeps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
+  return launch_chunked(h, n_substeps, /*io*/ nullptr, /*dbg*/ nullptr, /*active*/ nullptr, stream, /*rec*/ nullptr);
 }
 int agx_settle_debug(agx_handle h, int n_substeps, float* dbg, void* stream) {
   if (!h || n_substeps < 1 || !dbg) return fail(AGX_E_ARG, "agx_settle_debug: bad argument");
-  return launch_chunked(h, n_substeps, nullptr, nullptr, nullptr, nullptr, nullptr, dbg, false, stream);
+  return launch_chunked(h, n_substeps, /*io*/ nullptr, dbg, /*active*/ nullptr, stream, /*rec*/ nullptr);
 }
 int agx_step(agx_handle h, const float* a, float* obs, float* rew, uint8_t* done, float* info, void* stream) {
   if (!h || !a || !obs || !rew || !done) return fail(AGX_E_ARG, "agx_step: bad argument");
-  return launch_step(h, a, obs, rew, done, info, nullptr, stream);
+  const step_io io = {a, obs, rew, done, info};
+  return launch_chunked(h, h->frame_skip, &io, /*dbg*/ nullptr, /*active*/ nullptr, stream, /*rec*/ nullptr);
 }
 int agx_step_debug(agx_handle h, const float* a, float* obs, float* rew, uint8_t* done, float* info, float* dbg, void* stream) {
   if (!h || !a || !obs || !rew || !done || !dbg) return fail(AGX_E_ARG, "agx_step_debug: bad argument");
-  return launch_step(h, a, obs, rew, done, info, dbg, stream);
+  const step_io io = {a, obs, rew, done, info};
+  return launch_chunked(h, h->frame_skip, &io, dbg, /*active*/ nullptr, stream, /*rec*/ nullptr);
 }
+// agx_step with an event around every launch on its chunk stream: per chunk [build, solve] x frame_skip, then finish
 int agx_step_timed(agx_handle h, const float* a, float* obs, float* rew, uint8_t* done, float* info, void* stream, float* ms3, int* launches3) {
   if (!h || !a || !obs || !rew || !done || !ms3) return fail(AGX_E_ARG, "agx_step_timed: bad argument");
-  if (2 * h->frame_skip * h->sim_sub + 2 > 16 || h->cloth_dev) return fail(AGX_E_LIMIT, "agx_step_timed: too many launches per step for the event table (frame_skip x substeps), or a model with a cloth");
-  HIPCHK(hipSetDevice(h->device));
-  // the same chunked launch sequence as agx_step, with an event after every launch on its chunk stream
-  hipStream_t user = (hipStream_t)stream;
-  const int nc = h->n_chunks, per = (h->n_envs + nc - 1) / nc;
-  int nev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIPCHK(hipEventRecord(h->fork_ev, user));
-  for (int c = 0; c < nc; c++) {
-    const int e0 = c * per, ne = (e0 + per <= h->n_envs ? per : h->n_envs - e0);
-    if (ne <= 0) continue;
-    hipStream_t st = nc == 1 ? user : h->cs[c];
-    if (nc > 1) HIPCHK(hipStreamWaitEvent(st, h->fork_ev, 0));
-    int e = 0;
-    HIPCHK(hipEventRecord(h->kev[c][e++], st));
-    for (int k = 0; k < h->frame_skip; k++) {
-      (h->manifold ? h->V->build_mf : h->V->build)(st, ne, h->blob_dev, h->state_dev, k == 0 ? a : nullptr, h->scratch_dev, nullptr, e0, h->n_envs, h->sw, h->act_dim, (const uint8_t*)nullptr, h->overflow_dev, nullptr, 0, k);
-      HIPCHK(hipEventRecord(h->kev[c][e++], st));
-      h->V->solve(st, ne, h->blob_dev, h->state_dev, h->scratch_dev, nullptr, e0, h->n_envs, h->sw, (const uint8_t*)nullptr, k);
-      HIPCHK(hipEventRecord(h->kev[c][e++], st));
-    }
-    h->V->finish(st, ne, h->blob_dev, h->state_dev, a, h->scratch_dev, obs, rew, done, info, e0, h->n_envs, h->sw, h->act_dim, h->obs_dim, nullptr, 0, nullptr, 0);
-    HIPCHK(hipEventRecord(h->kev[c][e++], st));
-    HIPCHK(hipGetLastError());
-    nev[c] = e;
-    if (nc > 1) { HIPCHK(hipEventRecord(h->join_ev[c], st)); HIPCHK(hipStreamWaitEvent(user, h->join_ev[c], 0)); }
-  }
-  HIPCHK(hipStreamSynchronize(user));
+  if (2 * h->frame_skip * h->sim_sub + 2 > 16 || h->L.cloth) return fail(AGX_E_LIMIT, "agx_step_timed: too many launches per step for the event table (frame_skip x substeps), or a model with a cloth");
+  launch_recorder rec = {h->kev, {0, 0, 0, 0, 0, 0, 0, 0}};
+  const step_io io = {a, obs, rew, done, info};
+  const int rc = launch_chunked(h, h->frame_skip, &io, /*dbg*/ nullptr, /*active*/ nullptr, stream, &rec);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   ms3[0] = ms3[1] = ms3[2] = 0.f;
   int cnt[3] = {0, 0, 0};
-  for (int c = 0; c < nc; c++) for (int k = 0; k + 1 < nev[c]; k++) {
+  for (int c = 0; c < h->n_chunks; c++) for (int k = 0; k + 1 < rec.n[c]; k++) {
     float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, h->kev[c][k], h->kev[c][k + 1]));
-    const int t = k == nev[c] - 2 ? 2 : (k & 1);
+    const int t = k == rec.n[c] - 2 ? 2 : (k & 1);
     ms3[t] += ms; cnt[t]++;
   }
   if (launches3) { launches3[0] = cnt[0]; launches3[1] = cnt[1]; launches3[2] = cnt[2]; }
   return AGX_OK;
 }
+int agx_chunk_count(agx_handle h, int* out) { if (!h || !out) return fail(AGX_E_ARG, "agx_chunk_count: bad argument"); *out = h->n_chunks; return AGX_OK; }
 int agx_observe(agx_handle h, float* obs, void* stream) { return agx_observe_masked(h, obs, nullptr, stream); }
 int agx_observe_masked(agx_handle h, float* obs, const uint8_t* mask_dev, void* stream) {
   if (!h || !obs) return fail(AGX_E_ARG, "agx_observe: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  h->V->observe((hipStream_t)stream, h->n_envs, h->blob_dev, h->state_dev, obs, h->sw, h->obs_dim, mask_dev);
+  h->V->observe(h->L, (hipStream_t)stream, obs, mask_dev);
   HIPCHK(hipGetLastError());
   return AGX_OK;
 }
@@ -444,7 +417,7 @@ static int launch_sample(agx_handle h, uint64_t seed, const uint64_t* seeds_dev,
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   forget_warm(h, mask_dev, st);          // the sampled environments start without a warm-start memory
-  const float* settled = nullptr; int settled_sw = 0; const float* fell = nullptr;
+  agx_sample_args A = {(unsigned long long)seed, (const unsigned long long*)seeds_dev, impairment_mode, gender_mode, nullptr, 0, nullptr};
   if (h->reset_flags & 16) {
     // bed bathing (bed_bathing.py:119-137): the human is a rag doll dropped onto the bed -- the attached model samples its drop record from the
     // same seeds, settles for 100 simulation steps, and its state records tell this model's sampler where the human lies.
@@ -456,48 +429,40 @@ static int launch_sample(agx_handle h, uint64_t seed, const uint64_t* seeds_dev,
     if (two && !(hs->reset_flags & 256)) return fail(AGX_E_ARG, "reset: this model's reset lets the arm fall in a second handle (ModelBlob.fall_model()); attach that one, and the rag-doll model to it");
     agx_handle_s* hr = two ? hs->settle : hs;
     if (!hr) return fail(AGX_E_ARG, "reset: the fall model has no rag-doll model attached (agx_attach_settle_model)");
-    hr->V->sample(st, hr->n_envs, hr->blob_dev, hr->state_dev, (unsigned long long)seed, (const unsigned long long*)seeds_dev, mask_dev, impairment_mode,
-                  gender_mode, nullptr, hr->episode_dev, hr->sw, nullptr, hr->chosen_dev, nullptr, 0, nullptr);
+    hr->V->sample(hr->L, st, A, mask_dev, nullptr, nullptr);
     HIPCHK(hipGetLastError());
-    hr->active = mask_dev;
-    int rc = launch_chunked(hr, two ? hs->settle_substeps : h->settle_substeps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
-    hr->active = nullptr;
+    int rc = launch_chunked(hr, two ? hs->settle_substeps : h->settle_substeps, /*io*/ nullptr, /*dbg*/ nullptr, mask_dev, stream, /*rec*/ nullptr);
     if (rc) return rc;
-    settled = hr->state_dev; settled_sw = hr->sw;
+    A.settled = hr->L.state; A.settled_sw = hr->L.sw;
     if (two) {
       forget_warm(hs, mask_dev, st);
-      hs->V->sample(st, hs->n_envs, hs->blob_dev, hs->state_dev, (unsigned long long)seed, (const unsigned long long*)seeds_dev, mask_dev, impairment_mode,
-                    gender_mode, nullptr, hs->episode_dev, hs->sw, nullptr, hs->chosen_dev, settled, settled_sw, nullptr);
+      hs->V->sample(hs->L, st, A, mask_dev, nullptr, nullptr);
       HIPCHK(hipGetLastError());
-      hs->active = mask_dev;
-      rc = launch_chunked(hs, h->settle_substeps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
-      hs->active = nullptr;
+      rc = launch_chunked(hs, h->settle_substeps, /*io*/ nullptr, /*dbg*/ nullptr, mask_dev, stream, /*rec*/ nullptr);
       if (rc) return rc;
-      fell = hs->state_dev;
+      A.fell = hs->L.state;
     }
   }
-  h->V->sample(st, h->n_envs, h->blob_dev, h->state_dev, (unsigned long long)seed, (const unsigned long long*)seeds_dev, mask_dev, impairment_mode,
-               gender_mode, ik_info_dev, h->episode_dev, h->sw, nullptr, h->chosen_dev, settled, settled_sw, fell);
+  h->V->sample(h->L, st, A, mask_dev, ik_info_dev, nullptr);
   HIPCHK(hipGetLastError());
   // collision rejection (robot.py:105-112, env.py:299-308): the contacts of the sampled state come from the stepper's own build kernel;
   // a state whose arm / tool touches the human, the table or the wheelchair is re-sampled from the next IK restart.  Fixed schedule
   // of `collision_tries` rounds (no host round trip): the kernels of a round exit at once for the environments that are settled.
   for (int t = 0; t < h->collision_tries; t++) {
     const uint8_t* active = t == 0 ? mask_dev : h->work_dev;
-    h->V->build(st, h->n_envs, h->blob_dev, h->state_dev, nullptr, h->scratch_dev, nullptr, 0, h->n_envs, h->sw, h->act_dim, active, h->overflow_dev, nullptr, 0, 0);
+    h->V->build(h->L, st, 0, h->L.n_envs, nullptr, nullptr, active, 0, false);      // the plain build kernel, no trace: a collision pass
     HIPCHK(hipGetLastError());
-    h->V->verdict(st, h->n_envs, h->blob_dev, h->scratch_dev, active, h->work_dev, h->first_restart_dev, h->chosen_dev);
+    h->V->verdict(h->L, st, active, h->work_dev, h->first_restart_dev);
     HIPCHK(hipGetLastError());
-    h->V->sample(st, h->n_envs, h->blob_dev, h->state_dev, (unsigned long long)seed, (const unsigned long long*)seeds_dev, h->work_dev, impairment_mode,
-                 gender_mode, ik_info_dev, h->episode_dev, h->sw, h->first_restart_dev, h->chosen_dev, settled, settled_sw, fell);
-    HIPCHK(hipGetLastError());
-  }
-  if (h->cloth_dev && h->particles) {       // the water goes into the sampled cup
-    hipLaunchKernelGGL(agx_place_water_kernel, dim3(h->n_envs), dim3(64), 0, st, h->cloth_dev, h->state_dev, h->blob_dev, mask_dev, h->n_envs, h->sw, h->cloth_words);
+    h->V->sample(h->L, st, A, h->work_dev, ik_info_dev, h->first_restart_dev);
     HIPCHK(hipGetLastError());
   }
-  if (h->cloth_dev && !h->particles) {      // the garment goes where the sampled end effector is (dressing task words; the water has its own placement)
-    hipLaunchKernelGGL(agx_place_cloth_kernel, dim3(h->n_envs), dim3(256), 0, st, h->cloth_dev, h->state_dev, h->blob_dev, mask_dev, h->n_envs, h->sw, h->cloth_words);
+  if (h->L.cloth && h->particles) {       // the water goes into the sampled cup
+    hipLaunchKernelGGL(agx_place_water_kernel, dim3(h->L.n_envs), dim3(64), 0, st, h->L.cloth, h->L.state, h->L.blob, mask_dev, h->L.n_envs, h->L.sw, h->L.cloth_words);
+    HIPCHK(hipGetLastError());
+  }
+  if (h->L.cloth && !h->particles) {      // the garment goes where the sampled end effector is (dressing task words; the water has its own placement)
+    hipLaunchKernelGGL(agx_place_cloth_kernel, dim3(h->L.n_envs), dim3(256), 0, st, h->L.cloth, h->L.state, h->L.blob, mask_dev, h->L.n_envs, h->L.sw, h->L.cloth_words);
     HIPCHK(hipGetLastError());
   }
   return AGX_OK;
@@ -509,7 +474,7 @@ int agx_attach_settle_model(agx_handle h, agx_handle settle, int n_substeps) {
   const bool wants_fall = (h->reset_flags & 128) && !(h->reset_flags & 256);      // arm manipulation: the fall model goes here, the rag doll behind it
   if (wants_fall ? !(settle->reset_flags & 256) : !(settle->reset_flags & 32)) return fail(AGX_E_ARG, wants_fall ? "agx_attach_settle_model: this model takes its fall model (the same blob with AGX_X_FLAGS bit 8)" : "agx_attach_settle_model: the second handle is not a rag-doll model with a drop sampler");
   if (!settle->can_sample) return fail(AGX_E_ARG, "agx_attach_settle_model: the second handle has no sampler");
-  if (settle->n_envs != h->n_envs || settle->device != h->device) return fail(AGX_E_ARG, "agx_attach_settle_model: both handles must hold the same number of environments on the same device");
+  if (settle->L.n_envs != h->L.n_envs || settle->device != h->device) return fail(AGX_E_ARG, "agx_attach_settle_model: both handles must hold the same number of environments on the same device");
   h->settle = settle; h->settle_substeps = n_substeps;
   return AGX_OK;
 }
@@ -521,11 +486,9 @@ int agx_reset(agx_handle h, const uint8_t* mask_dev, const uint64_t* seeds_dev, 
   if (!h || settle_substeps < 0) return fail(AGX_E_ARG, "agx_reset: bad argument");
   int rc = launch_sample(h, seed, seeds_dev, mask_dev, impairment_mode, gender_mode, nullptr, stream);
   if (rc) return rc;
-  h->active = mask_dev;   // the settle substeps touch the masked environments only
-  rc = launch_chunked(h, settle_substeps, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, stream);
-  h->active = nullptr;
-  if (!rc && h->cloth_dev && !h->particles) {
-    hipLaunchKernelGGL(agx_cloth_gravity_kernel, dim3((h->n_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->state_dev, h->blob_dev, mask_dev, h->n_envs, h->sw);
+  rc = launch_chunked(h, settle_substeps, /*io*/ nullptr, /*dbg*/ nullptr, mask_dev, stream, /*rec*/ nullptr);   // the settle substeps touch the masked environments only
+  if (!rc && h->L.cloth && !h->particles) {
+    hipLaunchKernelGGL(agx_cloth_gravity_kernel, dim3((h->L.n_envs + 63) / 64), dim3(64), 0, (hipStream_t)stream, h->L.state, h->L.blob, mask_dev, h->L.n_envs, h->L.sw);
     HIPCHK(hipGetLastError());
   }
   return rc;
@@ -534,13 +497,13 @@ int agx_reset_done(agx_handle h, const float* pool_dev, int pool_n, const uint8_
 int agx_reset_done_at(agx_handle h, const float* pool_dev, int pool_n, const uint8_t* done_dev, int iteration, void* stream) {
   if (!h || !pool_dev || pool_n <= 0 || !done_dev) return fail(AGX_E_ARG, "agx_reset_done: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  if (h->cloth_dev && !h->cloth_pool_dev) return fail(AGX_E_ARG, "agx_reset_done: the model has a cloth; give the garments of the pool with agx_set_cloth_pool first");
-  hipLaunchKernelGGL(agx_reset_kernel, dim3(h->n_envs), dim3(64), 0, (hipStream_t)stream, h->state_dev, pool_dev, pool_n, done_dev, h->episode_dev, h->n_envs, h->sw, h->env_offset,
+  if (h->L.cloth && !h->cloth_pool_dev) return fail(AGX_E_ARG, "agx_reset_done: the model has a cloth; give the garments of the pool with agx_set_cloth_pool first");
+  hipLaunchKernelGGL(agx_reset_kernel, dim3(h->L.n_envs), dim3(64), 0, (hipStream_t)stream, h->L.state, pool_dev, pool_n, done_dev, h->L.episode, h->L.n_envs, h->L.sw, h->env_offset,
                      h->iter_word, iteration);
   forget_warm(h, done_dev, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
-  if (h->cloth_dev) {
-    hipLaunchKernelGGL(agx_reset_cloth_kernel, dim3(h->n_envs), dim3(256), 0, (hipStream_t)stream, h->cloth_dev, h->cloth_pool_dev, pool_n, done_dev, h->episode_dev, h->n_envs, h->cloth_words, h->env_offset);
+  if (h->L.cloth) {
+    hipLaunchKernelGGL(agx_reset_cloth_kernel, dim3(h->L.n_envs), dim3(256), 0, (hipStream_t)stream, h->L.cloth, h->cloth_pool_dev, pool_n, done_dev, h->L.episode, h->L.n_envs, h->L.cloth_words, h->env_offset);
     HIPCHK(hipGetLastError());
   }
   return AGX_OK;
@@ -548,31 +511,31 @@ int agx_reset_done_at(agx_handle h, const float* pool_dev, int pool_n, const uin
 // ---- garments of models with a cloth section: float[n_envs][2][NN][3], node positions then node velocities
 int agx_cloth_nodes(agx_handle h, int* nodes) { if (!h || !nodes) return fail(AGX_E_ARG, "agx_cloth_nodes: bad argument"); *nodes = h->cloth_nn; return AGX_OK; }
 int agx_set_cloth(agx_handle h, const float* host_cloth) {
-  if (!h || !host_cloth || !h->cloth_dev) return fail(AGX_E_ARG, "agx_set_cloth: bad argument or a model without a cloth");
+  if (!h || !host_cloth || !h->L.cloth) return fail(AGX_E_ARG, "agx_set_cloth: bad argument or a model without a cloth");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(h->cloth_dev, host_cloth, (size_t)h->n_envs * h->cloth_words * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->L.cloth, host_cloth, (size_t)h->L.n_envs * h->L.cloth_words * 4, hipMemcpyHostToDevice));
   return AGX_OK;
 }
 int agx_get_cloth(agx_handle h, float* host_cloth) {
-  if (!h || !host_cloth || !h->cloth_dev) return fail(AGX_E_ARG, "agx_get_cloth: bad argument or a model without a cloth");
+  if (!h || !host_cloth || !h->L.cloth) return fail(AGX_E_ARG, "agx_get_cloth: bad argument or a model without a cloth");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(host_cloth, h->cloth_dev, (size_t)h->n_envs * h->cloth_words * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(host_cloth, h->L.cloth, (size_t)h->L.n_envs * h->L.cloth_words * 4, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
-int agx_cloth_dev(agx_handle h, float** out_dev) { if (!h || !out_dev || !h->cloth_dev) return fail(AGX_E_ARG, "agx_cloth_dev: bad argument or a model without a cloth"); *out_dev = h->cloth_dev; return AGX_OK; }
+int agx_cloth_dev(agx_handle h, float** out_dev) { if (!h || !out_dev || !h->L.cloth) return fail(AGX_E_ARG, "agx_cloth_dev: bad argument or a model without a cloth"); *out_dev = h->L.cloth; return AGX_OK; }
 int agx_get_cloth_report(agx_handle h, float* host_report, int* words_per_env) {
-  if (!h || !h->cloth_dev || !h->report_dev) return fail(AGX_E_ARG, "agx_get_cloth_report: bad argument or a model without a cloth");
+  if (!h || !h->L.cloth || !h->L.report) return fail(AGX_E_ARG, "agx_get_cloth_report: bad argument or a model without a cloth");
   // a particle section's report is the water kernel's: one word per particle slot (agx_water.h REPORT_WORDS), the whole row
-  const int words = h->particles ? h->report_words : AGX_CLOTH_REPORT_WORDS(h->cloth_nn);
+  const int words = h->particles ? h->L.report_words : AGX_CLOTH_REPORT_WORDS(h->cloth_nn);
   if (words_per_env) *words_per_env = words;
   if (!host_report) return AGX_OK;
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy2D(host_report, (size_t)words * 4, h->report_dev, (size_t)h->report_words * 4, (size_t)words * 4, (size_t)h->n_envs, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy2D(host_report, (size_t)words * 4, h->L.report, (size_t)h->L.report_words * 4, (size_t)words * 4, (size_t)h->L.n_envs, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
 int agx_set_cloth_pool(agx_handle h, const float* pool_cloth_dev) {
-  if (!h || !h->cloth_dev) return fail(AGX_E_ARG, "agx_set_cloth_pool: bad argument or a model without a cloth");
+  if (!h || !h->L.cloth) return fail(AGX_E_ARG, "agx_set_cloth_pool: bad argument or a model without a cloth");
   h->cloth_pool_dev = pool_cloth_dev; return AGX_OK;
 }
 
@@ -581,11 +544,11 @@ int agx_check_collisions(agx_handle h, uint8_t* flags_host, void* stream) {
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   // the stepper's own collision pass on the states as they are (no motor targets, nothing is integrated: the states do not change)
-  h->V->build(st, h->n_envs, h->blob_dev, h->state_dev, nullptr, h->scratch_dev, nullptr, 0, h->n_envs, h->sw, h->act_dim, nullptr, h->overflow_dev, nullptr, 0, 0);
+  h->V->build(h->L, st, 0, h->L.n_envs, nullptr, nullptr, nullptr, 0, false);
   HIPCHK(hipGetLastError());
-  h->V->collision_flags(st, h->n_envs, h->blob_dev, h->scratch_dev, h->work_dev);
+  h->V->collision_flags(h->L, st, h->work_dev);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(flags_host, h->work_dev, (size_t)h->n_envs, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(flags_host, h->work_dev, (size_t)h->L.n_envs, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return AGX_OK;
 }
@@ -597,7 +560,7 @@ int agx_set_env_offset(agx_handle h, long long env_offset) {
 int agx_overflow_count(agx_handle h, int* out) {
   if (!h || !out) return fail(AGX_E_ARG, "agx_overflow_count: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(out, h->overflow_dev, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out, h->L.overflow, 4, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
 int agx_debug_layout(agx_handle h, int* out8) {
@@ -656,8 +619,8 @@ __global__ void agx_pack_kernel(const float* __restrict__ obs, const float* __re
 int agx_pack_step(agx_handle h, const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const float* info_dev, float* packed_dev, void* stream) {
   if (!h || !obs_dev || !reward_dev || !done_dev || !info_dev || !packed_dev) return fail(AGX_E_ARG, "agx_pack_step: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  const int total = h->n_envs * (h->obs_dim + 4);
-  hipLaunchKernelGGL(agx_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, reward_dev, done_dev, info_dev, packed_dev, h->n_envs, h->obs_dim);
+  const int total = h->L.n_envs * (h->L.obs_dim + 4);
+  hipLaunchKernelGGL(agx_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, obs_dev, reward_dev, done_dev, info_dev, packed_dev, h->L.n_envs, h->L.obs_dim);
   HIPCHK(hipGetLastError());
   return AGX_OK;
 }
@@ -699,20 +662,21 @@ int agx_allgather(agx_handle h, const float* local_dev, float* gathered_dev, siz
 int agx_step_host(agx_handle h, const float* a, float* obs, float* rew, uint8_t* done, float* info) {
   if (!h || !a || !obs || !rew || !done) return fail(AGX_E_ARG, "agx_step_host: bad argument");
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpy(h->act_dev, a, (size_t)h->n_envs * h->act_dim * 4, hipMemcpyHostToDevice));
-  int rc = launch_step(h, h->act_dev, h->obs_dev, h->rew_dev, h->done_dev, h->info_dev, nullptr, nullptr);
+  HIPCHK(hipMemcpy(h->act_dev, a, (size_t)h->L.n_envs * h->L.act_dim * 4, hipMemcpyHostToDevice));
+  const step_io io = {h->act_dev, h->obs_dev, h->rew_dev, h->done_dev, h->info_dev};
+  int rc = launch_chunked(h, h->frame_skip, &io, /*dbg*/ nullptr, /*active*/ nullptr, /*stream*/ nullptr, /*rec*/ nullptr);
   if (rc) return rc;
-  HIPCHK(hipMemcpy(obs, h->obs_dev, (size_t)h->n_envs * h->obs_dim * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rew, h->rew_dev, (size_t)h->n_envs * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(done, h->done_dev, (size_t)h->n_envs, hipMemcpyDeviceToHost));
-  if (info) HIPCHK(hipMemcpy(info, h->info_dev, (size_t)h->n_envs * AGX_INFO_DIM * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(obs, h->obs_dev, (size_t)h->L.n_envs * h->L.obs_dim * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rew, h->rew_dev, (size_t)h->L.n_envs * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(done, h->done_dev, (size_t)h->L.n_envs, hipMemcpyDeviceToHost));
+  if (info) HIPCHK(hipMemcpy(info, h->info_dev, (size_t)h->L.n_envs * AGX_INFO_DIM * 4, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
 int agx_observe_host(agx_handle h, float* obs) {
   if (!h || !obs) return fail(AGX_E_ARG, "agx_observe_host: bad argument");
   int rc = agx_observe(h, h->obs_dev, nullptr);
   if (rc) return rc;
-  HIPCHK(hipMemcpy(obs, h->obs_dev, (size_t)h->n_envs * h->obs_dim * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(obs, h->obs_dev, (size_t)h->L.n_envs * h->L.obs_dim * 4, hipMemcpyDeviceToHost));
   return AGX_OK;
 }
 

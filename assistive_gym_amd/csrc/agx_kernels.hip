@@ -34,10 +34,9 @@ AGX_K(kernel)(const uint32_t* __restrict__ blob, float* state, const float* acti
                                          trace ? trace + (size_t)env * trace_words + (size_t)phase * 12 * (((const int*)blob)[AGX_H_NDOF] + ((const int*)blob)[AGX_H_NFREE]) : nullptr); \
   if (dropped > 0 && threadIdx.x == 0) atomicAdd(overflow_total, dropped); \
 } \
-void launcher(hipStream_t st, int ne, const uint32_t* blob, float* state, const float* actions, float* scratch, float* debug, int e0, int n_envs, int sw, int act_dim, \
-              const uint8_t* active, int* overflow_total, float* trace, int trace_words, int phase) { \
-  hipLaunchKernelGGL(AGX_K(kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, blob, state, actions, scratch, debug, e0, n_envs, sw, act_dim, active, overflow_total, \
-                     trace, trace_words, phase); \
+void launcher(const agx_launch& L, hipStream_t st, int e0, int ne, const float* actions, float* debug, const uint8_t* active, int phase, bool trace) { \
+  hipLaunchKernelGGL(AGX_K(kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, L.blob, L.state, actions, L.scratch, debug, e0, L.n_envs, L.sw, L.act_dim, active, L.overflow, \
+                     trace ? L.trace : nullptr, trace ? L.trace_words : 0, phase); \
 }
 AGX_BUILD_KERNEL(agx_build_kernel, v_build, false)
 #if AGX_HAS_MANIFOLD
@@ -147,42 +146,39 @@ hipError_t v_init(void) {
 #endif
   return e;
 }
-void v_solve(hipStream_t st, int ne, const uint32_t* blob, float* state, float* scratch, float* debug, int e0, int n_envs, int sw, const uint8_t* active, int phase) {
-  hipLaunchKernelGGL(AGX_K(agx_solve_kernel), dim3(ne), dim3(64), g_solve_lds_bytes, st, blob, state, scratch, debug, e0, n_envs, sw, active, phase, g_solve_lds_bytes / 4);
+// the launchers: the handle's launch record unpacked into the kernels' arguments
+void v_solve(const agx_launch& L, hipStream_t st, int e0, int ne, float* debug, const uint8_t* active, int phase) {
+  hipLaunchKernelGGL(AGX_K(agx_solve_kernel), dim3(ne), dim3(64), g_solve_lds_bytes, st, L.blob, L.state, L.scratch, debug, e0, L.n_envs, L.sw, active, phase, g_solve_lds_bytes / 4);
 }
-void v_finish(hipStream_t st, int ne, const uint32_t* blob, float* state, const float* actions, float* scratch, float* obs, float* reward, uint8_t* done, float* info,
-              int e0, int n_envs, int sw, int act_dim, int obs_dim, const float* report, int report_words, float* cloth, int cloth_words) {
-  hipLaunchKernelGGL(AGX_K(agx_finish_kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, blob, state, actions, scratch, obs, reward, done, info, e0, n_envs, sw, act_dim, obs_dim,
-                     report, report_words, cloth, cloth_words);
+void v_finish(const agx_launch& L, hipStream_t st, int e0, int ne, const float* actions, float* obs, float* reward, uint8_t* done, float* info) {
+  hipLaunchKernelGGL(AGX_K(agx_finish_kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, L.blob, L.state, actions, L.scratch, obs, reward, done, info, e0, L.n_envs, L.sw, L.act_dim,
+                     L.obs_dim, L.report, L.report_words, L.cloth, L.cloth_words);
 }
 #if AGX_TASK == 5
-void v_cloth(hipStream_t st, int ne, const uint32_t* blob, const float* state, const float* trace, float* cloth, float* report, int e0, int n_envs, int sw,
-             int trace_words, int cloth_words, int report_words, int nsub, const uint8_t* active, int lds_bytes) {
-  (void)lds_bytes;
-  hipLaunchKernelGGL(AGX_K(agx_water_kernel), dim3(ne), dim3(64), 0, st, blob, state, trace, cloth, report, e0, n_envs, sw, trace_words, cloth_words, report_words, nsub, active);
+void v_cloth(const agx_launch& L, hipStream_t st, int e0, int ne, int nsub, const uint8_t* active) {
+  hipLaunchKernelGGL(AGX_K(agx_water_kernel), dim3(ne), dim3(64), 0, st, L.blob, L.state, L.trace, L.cloth, L.report, e0, L.n_envs, L.sw, L.trace_words, L.cloth_words,
+                     L.report_words, nsub, active);
 }
 int v_cloth_lds_bytes(int nn) { (void)nn; return 4 * agxw::LDS_WORDS; }
 #elif AGX_TASK == 3
-void v_cloth(hipStream_t st, int ne, const uint32_t* blob, const float* state, const float* trace, float* cloth, float* report, int e0, int n_envs, int sw,
-             int trace_words, int cloth_words, int report_words, int nsub, const uint8_t* active, int lds_bytes) {
-  hipLaunchKernelGGL(AGX_K(agx_cloth_kernel), dim3(ne), dim3(AGX_CLOTH_THREADS), lds_bytes, st, blob, state, trace, cloth, report, e0, n_envs, sw, trace_words, cloth_words,
-                     report_words, nsub, active);
+void v_cloth(const agx_launch& L, hipStream_t st, int e0, int ne, int nsub, const uint8_t* active) {
+  hipLaunchKernelGGL(AGX_K(agx_cloth_kernel), dim3(ne), dim3(AGX_CLOTH_THREADS), L.cloth_lds, st, L.blob, L.state, L.trace, L.cloth, L.report, e0, L.n_envs, L.sw, L.trace_words,
+                     L.cloth_words, L.report_words, nsub, active);
 }
 int v_cloth_lds_bytes(int nn) { return 4 * agxc::lds_words(nn); }
 #endif
-void v_observe(hipStream_t st, int n_envs, const uint32_t* blob, float* state, float* obs, int sw, int obs_dim, const uint8_t* mask) {
-  hipLaunchKernelGGL(AGX_K(agx_observe_kernel), dim3(n_envs), dim3(64), agx::LDS_BYTES, st, blob, state, obs, n_envs, sw, obs_dim, mask);
+void v_observe(const agx_launch& L, hipStream_t st, float* obs, const uint8_t* mask) {
+  hipLaunchKernelGGL(AGX_K(agx_observe_kernel), dim3(L.n_envs), dim3(64), agx::LDS_BYTES, st, L.blob, L.state, obs, L.n_envs, L.sw, L.obs_dim, mask);
 }
-void v_sample(hipStream_t st, int n_envs, const uint32_t* blob, float* state, unsigned long long seed0, const unsigned long long* seeds, const uint8_t* mask,
-              int impairment_mode, int gender_mode, float* info4, int* episode, int sw, const int* first_restart, int* chosen, const float* settled, int settled_sw, const float* fell) {
-  hipLaunchKernelGGL(AGX_K(agx_sample_kernel), dim3(n_envs), dim3(64), 0, st, blob, state, seed0, seeds, mask, impairment_mode, gender_mode, info4, episode, n_envs, sw,
-                     first_restart, chosen, settled, settled_sw, fell);
+void v_sample(const agx_launch& L, hipStream_t st, const agx_sample_args& A, const uint8_t* mask, float* info4, const int* first_restart) {
+  hipLaunchKernelGGL(AGX_K(agx_sample_kernel), dim3(L.n_envs), dim3(64), 0, st, L.blob, L.state, A.seed0, A.seeds, mask, A.impairment_mode, A.gender_mode, info4, L.episode, L.n_envs,
+                     L.sw, first_restart, L.chosen, A.settled, A.settled_sw, A.fell);
 }
-void v_verdict(hipStream_t st, int n_envs, const uint32_t* blob, const float* scratch, const uint8_t* active, uint8_t* work, int* first_restart, const int* chosen) {
-  hipLaunchKernelGGL(AGX_K(agx_reset_verdict_kernel), dim3(n_envs), dim3(64), 0, st, blob, scratch, active, work, first_restart, chosen, n_envs);
+void v_verdict(const agx_launch& L, hipStream_t st, const uint8_t* active, uint8_t* work, int* first_restart) {
+  hipLaunchKernelGGL(AGX_K(agx_reset_verdict_kernel), dim3(L.n_envs), dim3(64), 0, st, L.blob, L.scratch, active, work, first_restart, L.chosen, L.n_envs);
 }
-void v_collision_flags(hipStream_t st, int n_envs, const uint32_t* blob, const float* scratch, uint8_t* flags) {
-  hipLaunchKernelGGL(AGX_K(agx_collision_flags_kernel), dim3(n_envs), dim3(64), 0, st, blob, scratch, flags, n_envs);
+void v_collision_flags(const agx_launch& L, hipStream_t st, uint8_t* flags) {
+  hipLaunchKernelGGL(AGX_K(agx_collision_flags_kernel), dim3(L.n_envs), dim3(64), 0, st, L.blob, L.scratch, flags, L.n_envs);
 }
 
 #define AGX_STR2_(x) #x

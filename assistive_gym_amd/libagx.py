@@ -14,7 +14,7 @@ _LIB = None
 EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_per_env', 'agx_create', 'agx_destroy', 'agx_dims',
            'agx_set_state', 'agx_get_state', 'agx_state_dev', 'agx_settle', 'agx_settle_debug', 'agx_cloth_nodes', 'agx_set_cloth', 'agx_get_cloth', 'agx_cloth_dev', 'agx_set_cloth_pool', 'agx_get_cloth_report', 'agx_step', 'agx_step_debug', 'agx_step_timed', 'agx_debug_words',
            'agx_observe', 'agx_observe_masked', 'agx_reset_done_at', 'agx_sample_reset', 'agx_reset', 'agx_attach_settle_model', 'agx_reset_done', 'agx_step_host', 'agx_observe_host', 'agx_profile_begin', 'agx_profile_end',
-           'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_set_env_offset', 'agx_check_collisions',
+           'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_chunk_count', 'agx_set_env_offset', 'agx_check_collisions',
            'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae']
 
 
@@ -125,11 +125,10 @@ class Stepper:
             pass
 
     def n_chunks(self):
-        """independent chunks of environments a step is issued as (AGX_CHUNKS, default 3 from 2048 environments on)"""
-        e = os.environ.get('AGX_CHUNKS')
-        nc = int(e) if e else (1 if self.particles else (3 if self.n_envs >= 2048 else 1))
-        nc = min(max(nc, 1), 8)
-        return 1 if self.n_envs < 64 * nc else nc
+        """independent chunks of environments a step is issued as, decided in agx_create (agx_chunk_count; the rule is stated in include/agx.h)"""
+        out = C.c_int()
+        check(self.L.agx_chunk_count(self.h, C.byref(out)), 'agx_chunk_count')
+        return out.value
 
     def debug_layout(self):
         """[words per env, contacts offset, M^-1 offset, M^-1 row stride, row headers, impulses, phase timers, qdd] of the debug record"""

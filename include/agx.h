@@ -97,6 +97,10 @@ const char* agx_variant_name(agx_handle h);
 /* contacts dropped since agx_create because a budget was exceeded (contact, row or coefficient cap), summed over all envs:
  * they are missing from the dynamics and from total_force_on_human; 0 in a healthy run */
 int agx_overflow_count(agx_handle h, int* out);
+/* independent chunks of environments every step / settle of this handle is issued as, each on its own stream: AGX_CHUNKS as read by
+ * agx_create, else 3 from 2048 environments on and 1 below, 1 for the drinking scenes; within 1..8, and 1 where a chunk would hold fewer
+ * than 64 environments */
+int agx_chunk_count(agx_handle h, int* out);
 /* same as agx_step (same chunk streams) with a HIP event after every kernel launch; blocks until the step
  * is done and returns the summed launch durations of one step in ms3 = {build, solve, finish kernels} and
  * the number of launches of each in launches3 (may be NULL) */
