@@ -597,6 +597,37 @@ AGX_DEV void env_solve(const uint32_t* blob, float* gstate, float* gscratch, flo
   solve_tail(c, gstate, scr, sw, phase, dv0, dv1);
   if (gdebug && lane == 0) { gdebug[DBG_TIME + 5] = (float)(t1 - t0); gdebug[DBG_TIME + 6] = (float)(wave_clock() - t1); }
 }
+#if AGX_SOLVE_PAIR
+// solve of two consecutive environments in one wavefront (agx_pgs_lvw.h, pgs_lvw_pair): gstate and gscratch are the first environment's, the second's
+// lie sw and SCR_WORDS words behind; lds holds 2 x lds_words words.  Returns false, with nothing touched but LDS, when the two cannot share the
+// wide sweep (one of them is not eligible for it or overflows the scheduler two rows wide): the caller runs env_solve on each.
+AGX_DEV void env_solve_load(Ctx& c, Scratch& scr, const uint32_t* blob, float* gscratch, float* lds, int lane) {
+  ctx_init(c, blob, lds, lane);
+  scr = scratch_of(gscratch);
+  c.E = scr.ent; c.H = scr.hdr; c.gcon = scr.con;
+  c.ncon = scr.meta[META_NCON]; c.nrows = scr.meta[META_NROWS]; c.first_normal = scr.meta[META_NNC]; c.nent = scr.meta[META_NENT];
+}
+AGX_DEV bool env_solve_pair(const uint32_t* blob, float* gstate, float* gscratch, float* lds, int lane, int phase, int lds_words) {
+  if constexpr (!LVW_PAIRED) { (void)blob; (void)gstate; (void)gscratch; (void)lds; (void)lane; (void)phase; (void)lds_words; return false; }
+  else {
+    { Ctx c0, c1; Scratch s0, s1;
+      env_solve_load(c0, s0, blob, gscratch, lds, lane); env_solve_load(c1, s1, blob, gscratch + SCR_WORDS, lds + lds_words, lane);
+      if (!lvw_eligible(c0, lds_words) || !lvw_eligible(c1, lds_words)) return false;
+      if (!pgs_lvw_pair(c0, c1, lds, lds_words)) return false; }
+    // the tails, one environment after the other (ONE copy of the code; nothing of the sweeps' context stays in registers)
+    _Pragma("nounroll") for (int e = 0; e < 2; e++) {
+      Ctx c; Scratch scr;
+      env_solve_load(c, scr, blob, gscratch + (size_t)e * SCR_WORDS, lds + e * lds_words, lane);
+      const int sw = c.bi[AGX_H_STATE_WORDS];
+      float dv0, dv1;
+      lvw_pair_result(c, c.lds, dv0, dv1);
+      warm_remember(c, scr, lane);
+      solve_tail(c, gstate + (size_t)e * sw, scr, sw, phase, dv0, dv1);
+    }
+    return true;
+  }
+}
+#endif
 
 AGX_DEV void observe_dressing(const Ctx& c, float cloth_force_sum, float robot_force, float* gobs);
 AGX_DEV void env_observe(const uint32_t* blob, float* gstate, float* gobs, float* lds, int lane) {

@@ -44,10 +44,50 @@ AGX_BUILD_KERNEL(agx_build_kernel, v_build, false)
 AGX_BUILD_KERNEL(agx_build_mf_kernel, v_build_mf, true)
 #endif
 // solve: 50 PGS sweeps streaming the rows from the scratch record (L2), integration.  Lean.
-extern "C" __global__ void __launch_bounds__(64, 4)
+// Variants with the wide row-local sweep (AGX_SOLVE_PAIR, agx_pgs_lvw.h): a workgroup takes the environments env0 + 2 b and env0 + 2 b + 1 of
+// [env0, env_end) and sweeps them together, each in its own half of the LDS (2 x lds_words words); an environment without a partner (the end of the
+// launch, the `active` mask) or a pair that cannot share the sweep goes through env_solve, one environment after the other.  Debug launches: one
+// environment per workgroup.
+// (The kernel of a variant without the paired sweep, and of every variant with -DAGX_SOLVE_PAIR=0, keeps the arguments and the text it had before.)
+#if AGX_SOLVE_PAIR && AGX_PGS_LV == 4 && AGX_MAX_DOF <= 16 && AGX_MAX_BLOCK <= 10 && AGX_TASK == 0      /* = agx::LVW_PAIRED (AGX_TASK_FEEDING is 0) */
+#define AGX_SOLVE_PAIRED 1
+#define AGX_SOLVE_END_PARAM , int env_end
+#define AGX_SOLVE_END_ARG(x) , x
+#else
+#define AGX_SOLVE_PAIRED 0
+#define AGX_SOLVE_END_PARAM
+#define AGX_SOLVE_END_ARG(x)
+#endif
+constexpr bool SOLVE_PAIRED = agx::LVW_PAIRED;
+static_assert(SOLVE_PAIRED == (AGX_SOLVE_PAIRED != 0), "the preprocessor's statement of agx::LVW_PAIRED");
+// (paired: 160 VGPRs.  The sweeps' assembly owns v80..v127, and what the single path keeps beside the paired one does not fit the other 80 without
+// spilling; a paired launch has two wavefronts per SIMD where the unpaired one has four, so three are bound enough)
+#ifndef AGX_SOLVE_WAVES
+#define AGX_SOLVE_WAVES (SOLVE_PAIRED ? 3 : 4)
+#endif
+extern "C" __global__ void __launch_bounds__(64, AGX_SOLVE_WAVES)
 AGX_K(agx_solve_kernel)(const uint32_t* __restrict__ blob, float* state, float* scratch, float* debug, int env0, int n_envs, int sw, const uint8_t* __restrict__ active, int phase,
-                        int lds_words) {
+                        int lds_words AGX_SOLVE_END_PARAM) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+#if AGX_SOLVE_PAIRED
+  {
+    const bool pair = debug == nullptr;
+    const int envA = wave_uniform(env0 + (pair ? 2 : 1) * (int)blockIdx.x);      // (the sweeps take their record bases as scalar operands)
+    if (env_end > n_envs) env_end = n_envs;
+    const bool has0 = envA < env_end && (!active || active[envA]), has1 = pair && envA + 1 < env_end && (!active || active[envA + 1]);
+    int lane2 = (int)threadIdx.x;
+    asm volatile("" : "+v"(lane2));      // (no instruction: keeps the per-lane addresses of the single path below from being computed ahead of the paired sweeps and held across them)
+    if (has0 && has1 && agx::env_solve_pair(blob, state + (size_t)envA * sw, scratch + (size_t)envA * agx::SCR_WORDS, lds, lane2, phase, lds_words)) return;
+    _Pragma("nounroll") for (int e = 0; e < 2; e++) {
+      const int lane = (int)threadIdx.x;
+      // (both on the FIRST half of the LDS: the register sweep of agx_pgs.h addresses its window from LDS address 0)
+      if (e ? has1 : has0) agx::env_solve(blob, state + (size_t)(envA + e) * sw, scratch + (size_t)(envA + e) * agx::SCR_WORDS, debug ? debug + (size_t)(envA + e) * agx::DBG_WORDS : nullptr,
+                                          lds, lane, phase, lds_words);
+      wave_sync();
+    }
+    return;
+  }
+#endif
   const int env = env0 + blockIdx.x;
   if (env >= n_envs || (active && !active[env])) return;
   agx::env_solve(blob, state + (size_t)env * sw, scratch + (size_t)env * agx::SCR_WORDS, debug ? debug + (size_t)env * agx::DBG_WORDS : nullptr, lds, (int)threadIdx.x, phase,
@@ -133,8 +173,9 @@ AGX_K(agx_reset_verdict_kernel)(const uint32_t* __restrict__ blob, const float* 
 constexpr int SWEEP_LDS_BYTES = agx::LVS_COMPILED ? agx::LVS_SOLVE_LDS_BYTES : 0;      // what the row-local sweeps of this variant want (agx_pgs_lvs.h)
 int g_solve_lds_bytes = SWEEP_LDS_BYTES > agx::LDS_SOLVE_BYTES ? SWEEP_LDS_BYTES : agx::LDS_SOLVE_BYTES;
 hipError_t v_init(void) {
-  if (const char* e = getenv("AGX_SOLVE_LDS_BYTES")) { int b = atoi(e) & ~15; if (b >= agx::LDS_SOLVE_BYTES && b <= 64 * 1024) g_solve_lds_bytes = b; }
-  hipError_t e = hipFuncSetAttribute((const void*)AGX_K(agx_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, g_solve_lds_bytes);
+  // (per environment: a paired launch has twice as much, so the knob ends at 32 KB there)
+  if (const char* e = getenv("AGX_SOLVE_LDS_BYTES")) { int b = atoi(e) & ~15; if (b >= agx::LDS_SOLVE_BYTES && b <= (SOLVE_PAIRED ? 32 : 64) * 1024) g_solve_lds_bytes = b; }
+  hipError_t e = hipFuncSetAttribute((const void*)AGX_K(agx_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (SOLVE_PAIRED ? 2 : 1) * g_solve_lds_bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_build_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, agx::LDS_BYTES);
 #if AGX_HAS_MANIFOLD
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_build_mf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, agx::LDS_BYTES);
@@ -148,7 +189,9 @@ hipError_t v_init(void) {
 }
 // the launchers: the handle's launch record unpacked into the kernels' arguments
 void v_solve(const agx_launch& L, hipStream_t st, int e0, int ne, float* debug, const uint8_t* active, int phase) {
-  hipLaunchKernelGGL(AGX_K(agx_solve_kernel), dim3(ne), dim3(64), g_solve_lds_bytes, st, L.blob, L.state, L.scratch, debug, e0, L.n_envs, L.sw, active, phase, g_solve_lds_bytes / 4);
+  const bool pair = SOLVE_PAIRED && !debug;
+  hipLaunchKernelGGL(AGX_K(agx_solve_kernel), dim3(pair ? (ne + 1) / 2 : ne), dim3(64), (SOLVE_PAIRED ? 2 : 1) * g_solve_lds_bytes, st, L.blob, L.state, L.scratch, debug, e0, L.n_envs, L.sw,
+                     active, phase, g_solve_lds_bytes / 4 AGX_SOLVE_END_ARG(e0 + ne));
 }
 void v_finish(const agx_launch& L, hipStream_t st, int e0, int ne, const float* actions, float* obs, float* reward, uint8_t* done, float* info) {
   hipLaunchKernelGGL(AGX_K(agx_finish_kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, L.blob, L.state, actions, L.scratch, obs, reward, done, info, e0, L.n_envs, L.sw, L.act_dim,

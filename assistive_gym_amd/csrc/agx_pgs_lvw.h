@@ -24,13 +24,23 @@
 //   * its pair from the LDS window (or, a row beyond it, from the scratch record), its velocity slot from LDS, the
 //     4-step butterfly inside the DPP row, the impulse update in all 16 lanes alike, the scatter; impulses live in LDS (one word per row: the
 //     16 lanes of a group store the same value to the same address, no EXEC juggling).
-// 36 instructions per step (the narrow sweep: 38 per row).  LDS: velocity deltas, impulses, three step lists, the window -- 10 KB per wave.
+// 36 instructions per step (the narrow sweep: 38 per row).  LDS: velocity deltas, impulses, three step lists, the window -- 10 KB per environment.
+// Since AGX_SOLVE_PAIR (below, pgs_lvw_pair) a wavefront of the solve kernel holds two environments, each on two of the four lane groups and in its own
+// 10 KB half of the workgroup's 20 KB; the single-environment path of this file serves lone environments, pairs that cannot share the sweep and debug launches.
 #pragma once
 
 namespace agx {
 
 constexpr bool LVW_COMPILED = AGX_PGS_LV == 4 && LV_COMPILED;
 constexpr int LVW_NG = 4;                                            // lane groups = rows per step
+// AGX_SOLVE_PAIR (default 1; -DAGX_SOLVE_PAIR=0: one environment per wavefront, the kernels of round 6): a wavefront of the solve kernel sweeps
+// TWO environments, lane groups 0-1 the rows of the first and 2-3 those of the second (pgs_lvw_pair below).  The scene offers 1.4 rows per step and
+// two groups serve an environment as well as four (see above), so half of a one-environment wavefront issues every step for the idle row.
+#ifndef AGX_SOLVE_PAIR
+#define AGX_SOLVE_PAIR 1
+#endif
+constexpr bool LVW_PAIRED = AGX_SOLVE_PAIR != 0 && LVW_COMPILED;
+constexpr int LVW_NG_PAIR = 2;                                       // lane groups of an environment in a paired wavefront
 #ifndef AGX_LVW_MAX_STEPS            // (tests: a small limit makes ordinary substeps overflow the scheduler and take the fallback)
 #define AGX_LVW_MAX_STEPS 64
 #endif
@@ -53,11 +63,14 @@ AGX_DEV int lvw_window(int lds_words) {
 // the slots of a row are a 96-bit mask (second header table): nv <= 96
 AGX_DEV bool lvw_eligible(const Ctx& c, int lds_words) { return lvs_eligible(c, lds_words) && c.nv <= 96 && lds_words > LVW_PAIRS + 64 && PRM(c, AGX_P_SOLVE_WIDE) != 0.f; }
 
-struct LvwLay { float* lds; const float* H; const float* E; int dv_addr, lam_addr, pairs_addr, far8; };
+// (paired wavefronts: the addresses and far8 are per-lane values, those of the lane's environment; H and E are the first environment's and
+// rec the bytes from its scratch record to the lane's -- the second environment of a pair is the next one)
+struct LvwLay { float* lds; const float* H; const float* E; int dv_addr, lam_addr, pairs_addr, far8, rec; };
 
 // ---- the static schedule of the rows [r0, r0 + nr), in that order: lane = step.  ss: the (up to four) rows of this lane's step, a byte each,
-// idle slots = HW_DUMMY.  Returns the number of steps, -1 when they do not fit LVW_MAX_STEPS.
-AGX_DEV int lvw_schedule(const Ctx& c, int lane, int r0, int nr, uint32_t& ss) {
+// idle slots = HW_DUMMY.  Returns the number of steps, -1 when they do not fit LVW_MAX_STEPS.  ng: rows per step (a paired wavefront: LVW_NG_PAIR,
+// bytes 2 and 3 of ss stay idle).
+AGX_DEV int lvw_schedule(const Ctx& c, int lane, int r0, int nr, uint32_t& ss, int ng = LVW_NG) {
   // the slot masks of the rows r0 + lane and r0 + 64 + lane, read once (lane = row); the loop below takes a row's from its lane
   uint32_t a0 = 0u, a1 = 0u, a2 = 0u, b0 = 0u, b1 = 0u, b2 = 0u;
   if (lane < nr) { const int* Xi = (const int*)hx_row(c.H, r0 + lane); a0 = (uint32_t)Xi[H_MLO]; a1 = (uint32_t)Xi[H_MHI]; a2 = (uint32_t)Xi[H_M2]; }
@@ -67,7 +80,7 @@ AGX_DEV int lvw_schedule(const Ctx& c, int lane, int r0, int nr, uint32_t& ss) {
   auto place = [&](uint32_t m0, uint32_t m1, uint32_t m2, int r) {
     const uint64_t conflicts = wave_ballot(((u0 & m0) | (u1 & m1) | (u2 & m2)) != 0u);         // steps that hold a row sharing a slot with r
     const int e = conflicts ? 64 - clz64(conflicts) : 0;                                         // r goes behind the last of them
-    const uint64_t room = wave_ballot(fill < LVW_NG && lane < LVW_MAX_STEPS);
+    const uint64_t room = wave_ballot(fill < ng && lane < LVW_MAX_STEPS);
     const uint64_t cand = e >= 64 ? 0ull : (room >> e) << e;
     if (!cand) fits = false;                                                                     // (wave uniform; the rows that follow are placed for nothing)
     const int s = cand ? ffs64(cand) : -1;
@@ -101,12 +114,13 @@ AGX_DEV int lvw_compact(float* lds, int list, int lane, uint32_t ss, int act4) {
 // One step, the C++ statement of what the assembly loop does (what the emulator runs).
 AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
   const int g = lane >> 4, k = lane & (LV_G - 1), row = (int)((w >> (8 * g)) & 255u);
-  const float* Q = Y.H + HQ_BASE + HQ_STRIDE * row; const int* Qi = (const int*)Q; const int* P = (const int*)(Y.H + HP_BASE + HP_STRIDE * row);
+  const float* H = Y.H + (Y.rec >> 2); const float* E = Y.E + (Y.rec >> 2);
+  const float* Q = H + HQ_BASE + HQ_STRIDE * row; const int* Qi = (const int*)Q; const int* P = (const int*)(H + HP_BASE + HP_STRIDE * row);
   const int off8 = P[0] & 0xffff, n = (P[0] >> 16) & 255, na = (P[0] >> 24) & 255, ab = P[1];
   const bool on = k < n;
   const int slot = 4 * k + (k < na ? (ab & 0xffff) : ((ab >> 16) & 0xffff)) - H_AB_BIAS;
   float J = 0.f, B = 0.f, v = 0.f;
-  if (on) { if (off8 >= Y.far8) lv_ld2g(Y.E + (off8 >> 2) + 2 * k, J, B); else lv_ld2(Y.lds, Y.pairs_addr + off8 + 8 * k, J, B); v = lv_ld1(Y.lds, Y.dv_addr + slot); }
+  if (on) { if (off8 >= Y.far8) lv_ld2g(E + (off8 >> 2) + 2 * k, J, B); else lv_ld2(Y.lds, Y.pairs_addr + off8 + 8 * k, J, B); v = lv_ld1(Y.lds, Y.dv_addr + slot); }
   const float jdv = wave_sum16(on ? J * v : 0.f);
   const float l0 = lv_ld1(Y.lds, Y.lam_addr + 4 * row);
   float lo = Q[2], hi = Q[3];
@@ -143,11 +157,22 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
 #define LVW_S1B(RID)
 #define LVW_TAIL_LAST "v_add_u32_e32 %[sa], 16, %[sa]\n"
 #define LVW_PRIME LVW_S1("v88", "0") LVW_S1("v98", "4") LVW_S1("v108", "8") LVW_S1("v118", "12") "s_waitcnt lgkmcnt(0)\n"
+// (paired builds: the record offset of the lane's environment is folded into the per-lane constants hbk, pbk and k8, the LDS bases of its half into
+// k8p, k4dv and lambv, and far8 is a vector operand: the same instructions, per-lane operands where one environment per wavefront has scalars)
+#if AGX_SOLVE_PAIR
+#define LVW_PADDR(RID) "v_lshl_add_u32 v127, " RID ", 3, %[pbk]\n"
+#define LVW_LAMB "%[lambv]"
+#define LVW_FAR8_C "v"
+#else
+#define LVW_PADDR(RID) "v_lshlrev_b32_e32 v127, 3, " RID "\n"
+#define LVW_LAMB "%[lamb]"
+#define LVW_FAR8_C "s"
+#endif
 #define LVW_S2(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) \
   "v_lshl_add_u32 v126, " RID ", 4, %[hbk]\n" \
-  "v_lshlrev_b32_e32 v127, 3, " RID "\n" \
+  LVW_PADDR(RID) \
   "global_load_dword " HWA ", v126, %[hq]\n" \
-  "v_lshl_add_u32 " LA ", " RID ", 2, %[lamb]\n" \
+  "v_lshl_add_u32 " LA ", " RID ", 2, " LVW_LAMB "\n" \
   "global_load_dwordx2 " PP ", v127, %[hp]\n"
 // (the pair read comes last: a far step has none -- its pairs come from the scratch record in an out-of-line block, LVW_FAR -- and the wait behind S3
 // allows one LDS read in flight; two instructions between a VALU write of VCC and the v_cndmask that reads it: gfx940 hazard)
@@ -215,8 +240,8 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
   "v_sub_f32_e32 v121, v122, " L0 "\n" \
   "v_fmac_f32_e32 v123, " B ", v121\n" \
   LVW_END(LA, SON, IA, GNEXT, SUBEND)
-#define LVW_S2_A(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "v_lshl_add_u32 v126, " RID ", 4, %[hbk]\n" "v_lshlrev_b32_e32 v127, 3, " RID "\n"
-#define LVW_S2_B(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "global_load_dword " HWA ", v126, %[hq]\n" "v_lshl_add_u32 " LA ", " RID ", 2, %[lamb]\n"
+#define LVW_S2_A(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "v_lshl_add_u32 v126, " RID ", 4, %[hbk]\n" LVW_PADDR(RID)
+#define LVW_S2_B(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "global_load_dword " HWA ", v126, %[hq]\n" "v_lshl_add_u32 " LA ", " RID ", 2, " LVW_LAMB "\n"
 #define LVW_S2_C(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) "global_load_dwordx2 " PP ", v127, %[hp]\n"
 #define LVW_RID(P0, P1, PP, J, B, JB, HWA, L0, IA, LA, RID, LN, SON) RID
 // one step: C the slot of step t, N1 of t + 1, N3 of t + 3 (S1 of t + 4 re-uses C's row index register: its step has long passed S2)
@@ -253,11 +278,18 @@ AGX_DEV void lvw_step(const LvwLay& Y, int lane, uint32_t w, bool fric) {
       "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", \
       "v120", "v121", "v122", "v123", "v124", "v125", "v126", "v127", \
       "s50", "s51", "s52", "s53", "s54", "s55", "s56", "s57", "s58", "s59", "s60", "vcc", "scc", "memory"
+#if AGX_SOLVE_PAIR
+#define LVW_ASM_LAMB
+#define LVW_ASM_PBK , [pbk] "v"(Y.rec)
+#else
+#define LVW_ASM_LAMB [lamb] "s"(Y.lam_addr),
+#define LVW_ASM_PBK
+#endif
 #define LVW_ASM(FRIC) \
   asm volatile(LVW_BODY(FRIC) \
     : [sa] "+v"(sa) \
-    : [nst1] "s"(nsteps - 1), [hq] "s"(Hq), [hp] "s"(Hp), [E] "s"(Y.E), [far8] "s"(Y.far8), [lamb] "s"(Y.lam_addr), [lambv] "v"(Y.lam_addr), \
-      [kreg] "v"(k), [k8p] "v"(8 * k + Y.pairs_addr), [k8] "v"(8 * k), [k4dv] "v"(4 * k + Y.dv_addr - H_AB_BIAS), [hbk] "v"(4 * (lane & 3)) \
+    : [nst1] "s"(nsteps - 1), [hq] "s"(Hq), [hp] "s"(Hp), [E] "s"(Y.E), [far8] LVW_FAR8_C(Y.far8), LVW_ASM_LAMB [lambv] "v"(Y.lam_addr), \
+      [kreg] "v"(k), [k8p] "v"(8 * k + Y.pairs_addr), [k8] "v"(8 * k + Y.rec), [k4dv] "v"(4 * k + Y.dv_addr - H_AB_BIAS), [hbk] "v"(4 * (lane & 3) + Y.rec) LVW_ASM_PBK \
     : LVW_CLOBBERS)
 AGX_DEV void lvw_part_asm(const LvwLay& Y, int lane, int list_addr, int nsteps, bool fric) {
   const int k = lane & (LV_G - 1);
@@ -287,7 +319,7 @@ AGX_DEV bool pgs_lvw(Ctx& c, float* lds, int lds_words, float& dv0, float& dv1) 
   uint32_t ssA, ssF;
   const int nsA = lvw_schedule(c, lane, 0, nA, ssA), nsF = nsA < 0 ? -1 : lvw_schedule(c, lane, nA, nc, ssF);
   if (nsA < 0 || nsF < 0) return false;
-  LvwLay Y; Y.lds = lds; Y.H = c.H; Y.E = c.E; Y.dv_addr = lv_addr(lds, lds + LVW_DV); Y.lam_addr = lv_addr(lds, lds + LVW_LAM); Y.pairs_addr = lv_addr(lds, lds + LVW_PAIRS);
+  LvwLay Y; Y.lds = lds; Y.H = c.H; Y.E = c.E; Y.rec = 0; Y.dv_addr = lv_addr(lds, lds + LVW_DV); Y.lam_addr = lv_addr(lds, lds + LVW_LAM); Y.pairs_addr = lv_addr(lds, lds + LVW_PAIRS);
   const int LIST_FULL = LVW_LISTS, LIST_RED = LVW_LISTS + LVW_LIST, LIST_F = LVW_LISTS + 2 * LVW_LIST;
   float* LAM = lds + LVW_LAM;
   // ---- prologue: velocity deltas, impulses, the window of pairs, the first pair offset beyond it
@@ -342,5 +374,108 @@ AGX_DEV bool pgs_lvw(Ctx& c, float* lds, int lds_words, float& dv0, float& dv1) 
   wave_sync();
   return true;
 }
+
+#if AGX_SOLVE_PAIR
+// ---- two environments per wavefront.  Each environment of a pair has the LDS layout above in its own half of the launch's LDS (lds and
+// lds + lds_words), schedules its own rows two per step and keeps its own re-test and friction masks (lane = step, as alone); the three step
+// lists are joint -- word t: the first environment's two rows of its step t in bytes 0-1, the second's in bytes 2-3 -- and live in the first
+// half.  A part runs as many steps as the longer of the two lists; the shorter one ends in idle rows, which touch nothing but the idle impulse
+// of their own half.  Every environment visits its rows in the order it would alone (rows of a step share no slot), so the bits are the same.
+struct LvwSide { uint32_t ssA, ssF; int rowsA4, rowsF4, nc, nFull, nRed, nF, actF; float* LAM; };
+// One environment's half of a joint step list, as lvw_compact: the 16-bit words behind its last step are idle up to the end of the list
+AGX_DEV int lvw_compact2(float* lds0, int list, int lane, int side, uint32_t ss, int act2) {
+  typedef unsigned short __attribute__((may_alias)) u16a;
+  uint32_t w = ss & 0xffffu;
+  for (int j = 0; j < LVW_NG_PAIR; j++) if (!((act2 >> j) & 1)) w = (w & ~(0xffu << (8 * j))) | ((uint32_t)HW_DUMMY << (8 * j));
+  const uint64_t m = wave_ballot(act2 != 0);
+  const int n = popc64(m);
+  u16a* L = (u16a*)((int*)lds0 + list) + side;
+  for (int t = lane; t < LVW_LIST; t += 64) if (t >= n) L[2 * t] = (unsigned short)(LVW_IDLE & 0xffffu);
+  if (act2 != 0) L[2 * wave_rank(m)] = (unsigned short)w;
+  wave_fence();
+  return n;
+}
+// One environment of a pair up to the first sweep: schedules, LDS of its half, the layout of its lanes.  False when it cannot take the paired sweep
+// (nothing touched but LDS).
+AGX_DEV bool lvw_pair_prepare(const Ctx& c, float* lds0, float* lds, int lds_words, int side, LvwSide& S, LvwLay& Y) {
+  const int lane = c.lane;
+  const int nnc = c.first_normal, nc = c.ncon, nA = nnc + nc, R = c.nrows;
+  const int nsA = lvw_schedule(c, lane, 0, nA, S.ssA, LVW_NG_PAIR), nsF = nsA < 0 ? -1 : lvw_schedule(c, lane, nA, nc, S.ssF, LVW_NG_PAIR);
+  if (nsA < 0 || nsF < 0) return false;
+  S.nc = nc; S.LAM = lds + LVW_LAM; S.nRed = 0; S.nF = 0; S.actF = -1;
+  Y.lds = lds0; Y.rec = side * 4 * SCR_WORDS;
+  Y.dv_addr = lv_addr(lds0, lds + LVW_DV); Y.lam_addr = lv_addr(lds0, lds + LVW_LAM); Y.pairs_addr = lv_addr(lds0, lds + LVW_PAIRS);
+  const int win = lvw_window(lds_words);
+  lds[LVW_DV + lane] = 0.f; lds[LVW_DV + 64 + lane] = 0.f;
+  for (int r = lane; r < HW_ROWS; r += 64) S.LAM[r] = 0.f;
+  { const f2* src = (const f2*)c.E; f2* dst = (f2*)(lds + LVW_PAIRS); const int np = c.nent < win ? c.nent : win; for (int q = lane; q < np; q += 64) dst[q] = src[q]; }
+  { int far_first = 0x2000;
+    for (int r = lane; r < R; r += 64) { const int p0 = ((const int*)(c.H + HP_BASE))[HP_STRIDE * r]; const int off = (p0 & 0xffff) >> 3, n = (p0 >> 16) & 255; if (off + n > win && off < far_first) far_first = off; }
+    Y.far8 = 8 * (int)wave_min((float)far_first); }
+  S.rowsA4 = lane < nsA ? lvw_rows4(S.ssA) : 0; S.rowsF4 = lane < nsF ? lvw_rows4(S.ssF) : 0;
+  return true;
+}
+// The sweeps of two consecutive environments (c0: the first, its scratch record SCR_WORDS before c1's).  Returns false (nothing touched but LDS) when
+// one of them does not fit the scheduler two rows wide: the caller solves them one after the other.  Leaves the velocity deltas and the impulses of
+// each environment in its half of the LDS (LVW_DV, LVW_LAM): lvw_pair_result.
+AGX_DEV bool pgs_lvw_pair(const Ctx& c0, const Ctx& c1, float* lds0, int lds_words) {
+  const int lane = c0.lane, iters = (int)PRM(c0, AGX_P_NITER);
+  float* const lds1 = lds0 + lds_words;
+  LvwSide S[2]; LvwLay Ys[2];
+  if (!lvw_pair_prepare(c0, lds0, lds0, lds_words, 0, S[0], Ys[0])) return false;
+  if (!lvw_pair_prepare(c1, lds0, lds1, lds_words, 1, S[1], Ys[1])) return false;
+  // this lane's layout: lane groups 2 and 3 work for the second environment
+  const bool e = lane >= 32;
+  LvwLay Y; Y.lds = lds0; Y.H = c0.H; Y.E = c0.E;
+  Y.dv_addr = e ? Ys[1].dv_addr : Ys[0].dv_addr; Y.lam_addr = e ? Ys[1].lam_addr : Ys[0].lam_addr; Y.pairs_addr = e ? Ys[1].pairs_addr : Ys[0].pairs_addr;
+  Y.far8 = e ? Ys[1].far8 : Ys[0].far8; Y.rec = e ? Ys[1].rec : Ys[0].rec;
+  const int LIST_FULL = LVW_LISTS, LIST_RED = LVW_LISTS + LVW_LIST, LIST_F = LVW_LISTS + 2 * LVW_LIST;
+  const bool two_dirs = c0.nrows > c0.first_normal + 2 * c0.ncon || c1.nrows > c1.first_normal + 2 * c1.ncon;      // (an environment without contacts compacts an empty list)
+  wave_sync();
+  _Pragma("unroll") for (int s = 0; s < 2; s++) S[s].nFull = lvw_compact2(lds0, LIST_FULL, lane, s, S[s].ssA, S[s].rowsA4);
+  // the no-op re-test rule is per environment (noop_period: its period, or 0 = plain sweeps); an environment on plain sweeps beside one on the rule
+  // keeps its full list in its half of the reduced list as well.  (Both periods are the blob's AGX_P_NOOP_RETEST or 0, so the larger of the two is the
+  // period of every environment of the pair that follows the rule; two different non-zero periods do not occur.)
+  const int K0 = noop_period(c0), K1 = noop_period(c1), K = K0 > K1 ? K0 : K1;
+  const bool rule[2] = {K0 > 0, K1 > 0};
+  if (K > 0) _Pragma("unroll") for (int s = 0; s < 2; s++) if (!rule[s]) S[s].nRed = lvw_compact2(lds0, LIST_RED, lane, s, S[s].ssA, S[s].rowsA4);
+  _Pragma("nounroll") for (int it = 0; it < iters; it++) {
+    const bool retest = K > 0 && it % K == 0, use = K > 0 && !retest;
+    float bef[2][LVW_NG_PAIR];
+    if (retest) _Pragma("unroll") for (int s = 0; s < 2; s++) if (rule[s]) for (int j = 0; j < LVW_NG_PAIR; j++) bef[s][j] = S[s].LAM[lvw_row(S[s].ssA, j)];
+    { const int n0 = use ? S[0].nRed : S[0].nFull, n1 = use ? S[1].nRed : S[1].nFull;
+      lvw_part(Y, lane, use ? LIST_RED : LIST_FULL, n0 > n1 ? n0 : n1, false); }
+    if (retest) _Pragma("unroll") for (int s = 0; s < 2; s++) if (rule[s]) {
+      int act = 0;
+      for (int j = 0; j < LVW_NG_PAIR; j++) if (S[s].LAM[lvw_row(S[s].ssA, j)] != bef[s][j]) act |= 1 << j;
+      S[s].nRed = lvw_compact2(lds0, LIST_RED, lane, s, S[s].ssA, act & S[s].rowsA4);
+    }
+    _Pragma("nounroll") for (int dir = 0; dir < (two_dirs ? 2 : 1); dir++) {
+      _Pragma("unroll") for (int s = 0; s < 2; s++) {
+        const uint32_t ss = S[s].ssF; const int nc = S[s].nc;
+        int act = 0;
+        for (int j = 0; j < LVW_NG_PAIR; j++) {
+          const int r = lvw_row(ss, j);
+          if (r != HW_DUMMY) { const float lf = S[s].LAM[r + dir * nc], ln = S[s].LAM[r - nc]; if (ln != 0.f || lf != 0.f) act |= 1 << j; }
+        }
+        uint32_t ssd = ss;
+        if (dir) for (int j = 0; j < LVW_NG_PAIR; j++) if (lvw_row(ss, j) != HW_DUMMY) ssd += (uint32_t)nc << (8 * j);
+        act &= S[s].rowsF4;
+        if (two_dirs || wave_any(act != S[s].actF)) { S[s].nF = lvw_compact2(lds0, LIST_F, lane, s, ssd, act); S[s].actF = act; }
+      }
+      lvw_part(Y, lane, LIST_F, S[0].nF > S[1].nF ? S[0].nF : S[1].nF, true);
+    }
+  }
+  wave_sync();
+  return true;
+}
+// after pgs_lvw_pair, per environment (lds: its half): velocity deltas back to their DoF lanes, solved normal impulses -> contact records
+AGX_DEV void lvw_pair_result(Ctx& c, const float* lds, float& dv0, float& dv1) {
+  const int lane = c.lane;
+  dv0 = lds[LVW_DV + lane]; dv1 = lds[LVW_DV + 64 + lane];
+  if (lane < c.ncon) c.gcon[CON_STRIDE * lane + C_LAM] = lds[LVW_LAM + c.first_normal + lane];
+  wave_sync();
+}
+#endif
 
 }  // namespace agx
