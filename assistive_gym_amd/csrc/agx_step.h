@@ -18,7 +18,8 @@
 //
 // Files: agx_ctx.h (limits, LDS / scratch layouts, per-lane context), agx_dyn.h (kinematics, ABA, M^-1),
 // agx_collide.h (broadphase, GJK narrowphase, contact selection), agx_rows.h (constraint rows),
-// agx_pgs.h / agx_pgs_lvs.h / agx_pgs_lvw.h (Gauss-Seidel sweeps, gfx950 assembly), agx_env.h (integration, task layer, kernel bodies),
+// agx_pgs.h / agx_pgs_lvs.h / agx_pgs_lvw.h (Gauss-Seidel sweeps, gfx950 assembly), agx_env.h (integration, state load / store, build and solve
+// kernel bodies), agx_task.h (task layer: observation, force sums, events, reward; observe and finish kernel bodies),
 // agx_reset.h (device-side reset generator: sampling + IK restarts, float64).
 #pragma once
 #include "agx_math.h"
@@ -35,4 +36,5 @@
 #include "agx_water.h"
 #endif
 #include "agx_env.h"
+#include "agx_task.h"
 #include "agx_reset.h"

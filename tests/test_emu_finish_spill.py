@@ -1,4 +1,4 @@
-"""The finish kernel's spill query (csrc/agx_env.h, env_finish_feeding) on the CPU wave emulator: the default build proves "some spoon piece is
+"""The finish kernel's spill query (csrc/agx_task.h, env_finish_feeding) on the CPU wave emulator: the default build proves "some spoon piece is
 within SPILL_DIST of this particle" from the collider AABBs where that is decided by more than a millimetre and runs the narrowphase for the rest;
 -DAGX_FINISH_SPILL_GJK runs the narrowphase for every live particle, as the kernel did before.  Both must end every env step in the SAME BITS:
 observation, reward, done, info and the whole state record (alive / active masks, RNG words, success counter included).

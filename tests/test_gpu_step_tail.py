@@ -1,6 +1,6 @@
 """-m gpu: the tail of an env step computes the same bits as before.
 The finish kernel of the feeding variant proves the spill query ("some spoon piece within SPILL_DIST of this particle") from the collider AABBs
-where that is decided by more than a millimetre and runs the narrowphase only for the rest (csrc/agx_env.h, env_finish_feeding);
+where that is decided by more than a millimetre and runs the narrowphase only for the rest (csrc/agx_task.h, env_finish_feeding);
 lib/variants/finishgjk.so (-DAGX_FINISH_SPILL_GJK, built by __graft_entry__.build()) runs it for every live particle, as the kernel did up to
 round 6.  64 FeedingJaco environments -- 16 copies each of a particle resting on the spoon, in the shell around the limit (both sides), far away
 and at the mouth (tests/golden/finish_spill_cases.npz; tests/test_emu_finish_spill.py shows on the CPU which path each takes) -- stepped 8 times
