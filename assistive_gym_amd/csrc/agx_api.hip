@@ -107,7 +107,25 @@ extern "C" __global__ void __launch_bounds__(64) agx_selftest_kernel(float* out_
   out_f[256 + lane] = wave_max(x);
 }
 
+// the arm chain the IK code is compiled for (agx_reset.h rs_ik, agx_ik.h): `narm` joints in a serial chain -- each joint's parent is the one before, the
+// first hangs off the base -- the k-th one driven by action act0 + k, the last one carrying the end-effector frame of link `ee_link`
+bool arm_chain_ok(const int32_t* hi, const int32_t* chain, int narm, int act0, int ee_link) {
+  for (int k = 0; k < narm; k++) {
+    const int d = chain[k];
+    if (d < 0 || d >= hi[AGX_H_NROBOT]) return false;
+    const int32_t* R = hi + hi[AGX_H_OFF_ROBOT] + d * AGX_R_STRIDE;
+    if (R[AGX_R_PARENT] != (k ? chain[k - 1] : -1) || R[AGX_R_ACT] != act0 + k) return false;
+    if (k == narm - 1 && ee_link != d) return false;
+  }
+  return true;
+}
+
 }  // namespace
+
+// csrc/agx_ik.hip
+void agx_launch_ee_pose(hipStream_t st, const uint32_t* blob, const float* state, int sw, int n_envs, int arms, float* pose);
+void agx_launch_ee_ik(hipStream_t st, const uint32_t* blob, const float* state, int sw, int n_envs, int arms, const float* target, int target_stride,
+                      int frame, int iters, float damping, float gain, float* q_out, float* action, int action_stride, float* err);
 
 struct agx_handle_s {
   const agx_variant* V;   // the compiled kernel variant serving this model
@@ -126,6 +144,7 @@ struct agx_handle_s {
   bool particles;       // the "cloth" section holds the water particles of the drinking scene (AGX_CL_PARTICLES), not a garment
   const float* cloth_pool_dev;   // the garments of the reset pool (agx_set_cloth_pool)
   bool can_sample;      // the variant has a reset generator (agx_reset.h) and the blob fits it
+  int ee_arms;          // arm chains agx_ee_pose / agx_ee_ik serve (agx_ee_arms): 0 for a robot on wheels or a chain that fails arm_chain_ok
   // staging for the *_host convenience calls
   float *act_dev, *obs_dev, *rew_dev, *info_dev; uint8_t* done_dev;
   hipEvent_t ev0, ev1;
@@ -185,6 +204,7 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
       return fail(AGX_E_LIMIT, "agx_create: a pair group has a collider range of more than 128 colliders");
   }
   bool can_sample = true;   // every variant carries the reset generator; what follows finds the models it cannot sample
+  int ee_arms = 0;
   {   // (scope of X and T)  Its IK is compiled for a serial 7-DoF arm carrying the end effector
     const int32_t* X = hi + hi[AGX_H_OFF_RESET];
     const int32_t* T = hi + hi[AGX_H_OFF_TASK];
@@ -196,21 +216,17 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
         X[AGX_X_TOC_NGOALS] > 4 || X[AGX_X_PED_N] > 2) can_sample = false;
     if (ragdoll && hi[AGX_H_NDOF] != 6 + X[AGX_X_NJOINT] - 1) can_sample = false;    // virtual joints + every joint of the tree but the fixed waist
     if (mobile && !ragdoll && (X[AGX_X_MOBILE_LIFT_DOF] < 0 || X[AGX_X_MOBILE_LIFT_DOF] >= hi[AGX_H_NROBOT] || X[AGX_X_TOC_ATTEMPTS] != 0 || X[AGX_X_IK_RESTARTS] != 0)) can_sample = false;
-    for (int k = 0; can_sample && !mobile && k < V->rs_narm; k++) {
-      const int d = X[AGX_X_CHAIN + k];
-      if (d < 0 || d >= hi[AGX_H_NROBOT]) { can_sample = false; break; }
-      const int32_t* R = hi + hi[AGX_H_OFF_ROBOT] + d * AGX_R_STRIDE;
-      const int dup = hi[AGX_H_TASK_KIND] == AGX_TASK_ARM_MANIPULATION ? T[AGX_T_DUP_ACT] : 0;     // robot_arm = 'both' lists a single arm twice: the second copy's actions drive it (robot.py:16)
-      if (R[AGX_R_PARENT] != (k ? X[AGX_X_CHAIN + k - 1] : -1) || R[AGX_R_ACT] != k + dup) can_sample = false;
-      if (k == V->rs_narm - 1 && T[AGX_T_EE_LINK] != d) can_sample = false;
-    }
-    for (int k = 0; can_sample && (X[AGX_X_FLAGS] & 512) && k < V->rs_narm; k++) {     // a two-armed robot: the second chain, driven by the actions behind the first arm's
-      const int d = X[AGX_X_CHAIN2 + k];
-      if (d < 0 || d >= hi[AGX_H_NROBOT]) { can_sample = false; break; }
-      const int32_t* R = hi + hi[AGX_H_OFF_ROBOT] + d * AGX_R_STRIDE;
-      if (R[AGX_R_PARENT] != (k ? X[AGX_X_CHAIN2 + k - 1] : -1) || R[AGX_R_ACT] != V->rs_narm + k) can_sample = false;
-      if (k == V->rs_narm - 1 && (T[AGX_T_EE2_LINK] != d || T[AGX_T_TOOL2_BODY] <= 0 || T[AGX_T_TOOL2_BODY] >= hi[AGX_H_NFREE])) can_sample = false;
-    }
+    // the arm: AGX_X_CHAIN, driven by the first actions (robot_arm = 'both' lists a single arm twice: the second copy's actions drive it, robot.py:16)
+    const int dup = hi[AGX_H_TASK_KIND] == AGX_TASK_ARM_MANIPULATION ? T[AGX_T_DUP_ACT] : 0;
+    const bool two = (X[AGX_X_FLAGS] & 512) != 0;     // a two-armed robot: the second chain, driven by the actions behind the first arm's
+    const bool chain1 = !mobile && arm_chain_ok(hi, X + AGX_X_CHAIN, V->rs_narm, dup, T[AGX_T_EE_LINK]);
+    const bool chain2 = two && arm_chain_ok(hi, X + AGX_X_CHAIN2, V->rs_narm, V->rs_narm, T[AGX_T_EE2_LINK]);
+    if (!mobile && !chain1) can_sample = false;
+    if (two && !(chain2 && T[AGX_T_TOOL2_BODY] > 0 && T[AGX_T_TOOL2_BODY] < hi[AGX_H_NFREE])) can_sample = false;
+    // end-effector control (agx_ik.h) serves the same chains of 7 joints, on a fixed base, whose action columns lie inside the action row
+    const bool has_reset = hi[AGX_H_OFF_TARGETS] - hi[AGX_H_OFF_RESET] >= AGX_X_COUNT || hi[AGX_H_NWORDS] - hi[AGX_H_OFF_RESET] >= AGX_X_COUNT;     // (as reset_flags below)
+    if (has_reset && X[AGX_X_NARM] == 7 && V->rs_narm == 7 && hi[AGX_H_BASE_LINK] == 0 && chain1 && (!two || chain2) && dup >= 0 && 7 * (two ? 2 : 1) + dup <= hi[AGX_H_ACT_DIM])
+      ee_arms = two ? 2 : 1;
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(AGX_E_NOGPU, "agx_create: no HIP device (libagx has no CPU path)");
@@ -218,7 +234,7 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
   HIPCHK(hipSetDevice(device));
   agx_handle h = new agx_handle_s();
   memset(h, 0, sizeof *h);
-  h->can_sample = can_sample; h->V = V;
+  h->can_sample = can_sample; h->ee_arms = ee_arms; h->V = V;
   const bool manifold = ((const float*)blob)[hi[AGX_H_OFF_PARAMS] + AGX_P_MANIFOLD] > 0.f;
   h->step_build = manifold ? V->build_mf : V->build;
   if (manifold && !V->build_mf) { delete h; return fail(AGX_E_LIMIT, "agx_create: AGX_P_MANIFOLD is set, but this kernel variant is compiled without the manifold stage (feeding, bed_bathing, scratch_itch, arm_manipulation have it)"); }
@@ -657,6 +673,36 @@ int agx_allgather(agx_handle h, const float* local_dev, float* gathered_dev, siz
   int rc = rccl_load(); if (rc) return rc;
   rc = g_rccl.AllGather(local_dev, gathered_dev, floats_per_rank, 7 /* ncclFloat32 */, comm, (hipStream_t)stream);
   return rc ? rccl_fail("ncclAllGather", rc) : AGX_OK;
+}
+
+// ---- end-effector control (csrc/agx_ik.h, csrc/agx_ik.hip): every check before any launch
+int agx_ee_arms(agx_handle h, int* arms) {
+  if (!h || !arms) return fail(AGX_E_ARG, "agx_ee_arms: bad argument");
+  *arms = h->ee_arms; return AGX_OK;
+}
+int agx_ee_pose(agx_handle h, float* pose_dev, void* stream) {
+  if (!h || !pose_dev) return fail(AGX_E_ARG, "agx_ee_pose: bad argument");
+  if (h->ee_arms == 0) return fail(AGX_E_ARG, "agx_ee_pose: this model has no arm chain on a fixed base (agx_ee_arms is 0: a robot on wheels, or a chain the IK is not compiled for)");
+  HIPCHK(hipSetDevice(h->device));
+  agx_launch_ee_pose((hipStream_t)stream, h->L.blob, h->L.state, h->L.sw, h->L.n_envs, h->ee_arms, pose_dev);
+  HIPCHK(hipGetLastError());
+  return AGX_OK;
+}
+int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int frame, int iters, float damping, float gain,
+              float* q_out_dev, float* action_dev, int action_stride, float* err_dev, void* stream) {
+  if (!h) return fail(AGX_E_ARG, "agx_ee_ik: null handle");
+  if (!target_dev) return fail(AGX_E_ARG, "agx_ee_ik: null target");
+  if (h->ee_arms == 0) return fail(AGX_E_ARG, "agx_ee_ik: this model has no arm chain on a fixed base (agx_ee_arms is 0: a robot on wheels, or a chain the IK is not compiled for)");
+  if (frame != AGX_EE_ABSOLUTE && frame != AGX_EE_DELTA) return fail(AGX_E_ARG, "agx_ee_ik: unknown frame (AGX_EE_ABSOLUTE, AGX_EE_DELTA)");
+  if (iters < 1 || iters > 1000) return fail(AGX_E_ARG, "agx_ee_ik: iters outside 1..1000");
+  if (!(damping > 0.f)) return fail(AGX_E_ARG, "agx_ee_ik: damping must be positive");
+  if (target_stride < h->ee_arms * (frame == AGX_EE_DELTA ? 6 : 7)) return fail(AGX_E_ARG, "agx_ee_ik: target_stride is smaller than arms x 7 (absolute) / arms x 6 (delta) floats");
+  if (action_dev && action_stride < h->L.act_dim) return fail(AGX_E_ARG, "agx_ee_ik: action_stride is smaller than the action dimension");
+  HIPCHK(hipSetDevice(h->device));
+  agx_launch_ee_ik((hipStream_t)stream, h->L.blob, h->L.state, h->L.sw, h->L.n_envs, h->ee_arms, target_dev, target_stride, frame, iters, damping, gain,
+                   q_out_dev, action_dev, action_stride, err_dev);
+  HIPCHK(hipGetLastError());
+  return AGX_OK;
 }
 
 int agx_step_host(agx_handle h, const float* a, float* obs, float* rew, uint8_t* done, float* info) {

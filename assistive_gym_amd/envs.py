@@ -63,10 +63,93 @@ def _box(n, bound):
 
 class _Agent:
     """The attributes of the reference's Robot / Human / Tool objects that learn.py, env_viewer.py and user scripts read
-    (controllable_joint_indices, agent.py:21; Robot tables, robot.py:6-39).  Physics calls on them do not exist here."""
+    (controllable_joint_indices, agent.py:21; Robot tables, robot.py:6-39).  Physics calls on them do not exist here -- but for the robot's
+    end-effector calls, _Robot below."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+
+class _EndEffector(int):
+    """A handle robot.get_pos_orient / robot.ik accept: the reference's link number of the end effector (an int, as robot.right_end_effector
+    is there) that also says which arm chain of the stepper it names.  -1 where the robot tables (model/compiler.py) do not carry the number:
+    a sentinel only these two calls take."""
+
+    def __new__(cls, link, arm):
+        self = super().__new__(cls, link)
+        self.arm = arm
+        return self
+
+
+class _Robot(_Agent):
+    """The robot of a scalar env: the attribute bag plus the end-effector calls of the reference's teleoperation loop (teleop_example.py:
+    robot.get_pos_orient(robot.right_end_effector), robot.get_joint_angles(robot.right_arm_joint_indices), robot.ik(...)), answered by the
+    stepper's agx_ee_pose / agx_ee_ik for the env's one environment.  The IK is the damped-least-squares iteration of host/kin.py in float32 on
+    the device, not Bullet's; a link other than an end effector, contacts and closest points are not built."""
+
+    def _bind(self, env, base):
+        from .model import compiler as L
+        self._env, self._base = env, base
+        x0 = base.h['OFF_RESET']
+        two = base.has_reset_generator and bool(int(base.i[x0 + L.X_['FLAGS']]) & 512)
+        chains = [[int(d) for d in base.i[x0 + L.X_[k]:x0 + L.X_[k] + 7]] for k in (['CHAIN', 'CHAIN2'] if two else ['CHAIN'])] if base.has_reset_generator else []
+        name = base.meta.get('robot')
+        for arm, chain in enumerate(chains):
+            if any(d < 0 or d >= base.nrobot for d in chain) or len(set(chain)) != 7:
+                continue                                           # a robot on wheels: its chain words are unused
+            pb = [base.robot_i(d, 'PB_INDEX') for d in chain]
+            # the reference's link number and the side of this arm, where a robot table lists these joints (the right arms of PR2 / Baxter have a
+            # table of their own; a single-arm robot answers to both sides, as its right_* and left_* lists are the same in the reference)
+            tables = [('right', L.ROBOT_RIGHT.get(name)), ('left' if name in L.ROBOT_RIGHT else 'both', L.ROBOT_BASE.get(name)), ('both', L.FEEDING_ROBOTS.get(name))]
+            side, link = next(((sd, t['ee_pb']) for sd, t in tables if t and list(t.get('arm', ())) == pb), ('left' if arm else ('right' if two else 'both'), -1))
+            for sd in (('right', 'left') if side == 'both' else (side,)):
+                setattr(self, sd + '_end_effector', _EndEffector(link, arm))
+                setattr(self, sd + '_arm_joint_indices', list(pb))
+                setattr(self, sd + '_arm_ik_indices', list(range(7)))       # robot.ik returns the arm's seven angles: the indices into Bullet's solution vector have no meaning here
+        self._chains = chains
+
+    def _arm(self, link):
+        if not isinstance(link, _EndEffector):
+            raise NotImplementedError('only the end effector is built: pass robot.right_end_effector / robot.left_end_effector (link frames, contacts and closest points of other links are not)')
+        return link.arm
+
+    def _poses(self):
+        import torch
+        st = self._env._ensure_stepper()
+        out = torch.zeros((1, max(1, st.ee_arms()), 7), dtype=torch.float32, device='cuda:%d' % self._env.device)
+        st.ee_pose(out)                                            # raises for a robot on wheels (agx_ee_arms is 0)
+        st.synchronize()
+        return out
+
+    def get_pos_orient(self, link, center_of_mass=False, convert_to_realworld=False):
+        """agent.py:130-140 for the end effector: (world position [3], quaternion x y z w [4]) of its link frame"""
+        if center_of_mass or convert_to_realworld:
+            raise NotImplementedError('get_pos_orient: only the link frame in world coordinates is built')
+        pose = self._poses()[0, self._arm(link)].cpu().numpy().astype(np.float64)
+        return pose[:3], pose[3:]
+
+    def get_joint_angles(self, indices=None):
+        """agent.py:84-90: angles of the joints with these PyBullet indices (default: the controllable ones)"""
+        base = self._base
+        dof = {base.robot_i(d, 'PB_INDEX'): d for d in range(base.nrobot)}
+        q = base.view(self._env._ensure_stepper().get_state())['q'][0]
+        return np.array([q[dof[j]] for j in (self.controllable_joint_indices if indices is None else indices)], dtype=np.float64)
+
+    def ik(self, target_joint, target_pos, target_orient=None, ik_indices=None, max_iterations=200, use_current_as_rest=False, **ignored):
+        """agent.py:252-274: target joint angles of the arm that carries `target_joint` for a world pose; target_orient None keeps the current
+        orientation.  Up to max_iterations (at most 1000) damped-least-squares iterations from the current angles, stopping at 1e-4; limits are the
+        joint limits (Bullet's rest poses, joint ranges and its null-space term are not reproduced)."""
+        import torch
+        arm = self._arm(target_joint)
+        st = self._env._ensure_stepper()
+        target = self._poses().clone()                             # the other arm of a two-armed robot aims at where it is
+        target[0, arm, :3] = torch.as_tensor(np.asarray(target_pos, dtype=np.float32))
+        if target_orient is not None:
+            target[0, arm, 3:] = torch.as_tensor(np.asarray(target_orient, dtype=np.float32))
+        q_out = torch.zeros_like(target)
+        st.ee_ik(target.reshape(1, -1), 'absolute', iters=max(1, min(int(max_iterations), 1000)), q_out=q_out)
+        st.synchronize()
+        return q_out[0, arm].cpu().numpy().astype(np.float64)
 
 
 class AssistiveEnv(_Base):
@@ -98,8 +181,9 @@ class AssistiveEnv(_Base):
         hum_pb = [self.blob.robot_i(d, 'PB_INDEX') for d in range(base.nrobot, base.ndof)] if self.coop else []
         mobile = base.h['BASE_LINK'] > 0                                              # robot.py:11: 'wheel' in controllable_joints
         d0 = next(d for d in range(base.nrobot) if base.robot_i(d, 'ACT') >= 0)
-        self.robot = _Agent(controllable_joint_indices=arm_pb, mobile=mobile, motor_gains=base.robot_f(d0, 'KP'), motor_forces=base.robot_f(d0, 'MAXF'),
+        self.robot = _Robot(controllable_joint_indices=arm_pb, mobile=mobile, motor_gains=base.robot_f(d0, 'KP'), motor_forces=base.robot_f(d0, 'MAXF'),
                             wheel_joint_indices=[base.robot_i(d, 'PB_INDEX') for d in range(base.nrobot) if base.robot_i(d, 'OBS_SKIP') and base.robot_i(d, 'ACT_SRC') == 0 and base.robot_i(d, 'ACT') >= 0])
+        self.robot._bind(self, base)
         self.human = _Agent(controllable_joint_indices=hum_pb, controllable=self.coop)
         self.tool = _Agent()
         self.camera_width, self.camera_height, self.view_matrix, self.projection_matrix = None, None, None, None
@@ -165,6 +249,18 @@ class AssistiveEnv(_Base):
         assert self.view_matrix is not None, 'You must call env.setup_camera() or env.setup_camera_rpy() before getting a camera image'   # env.py:355
         # rendering is out of scope: a blank frame of the requested size keeps learn.render_policy's loop (learn.py:96-131) running
         return np.zeros((self.camera_height, self.camera_width, 4), dtype=np.uint8), np.ones((self.camera_height, self.camera_width), dtype=np.float32)
+
+    def get_euler(self, quaternion):
+        """env.py:342-343 (p.getEulerFromQuaternion): fixed-axis roll, pitch, yaw of a quaternion (x, y, z, w)"""
+        x, y, z, w = np.asarray(quaternion, dtype=np.float64) / np.linalg.norm(quaternion)
+        return np.array([np.arctan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y)), np.arcsin(np.clip(2 * (w * y - z * x), -1.0, 1.0)),
+                         np.arctan2(2 * (w * z + x * y), 1 - 2 * (y * y + z * z))])
+
+    def get_quaternion(self, euler):
+        """env.py:345-346 (p.getQuaternionFromEuler); a quaternion (4 values) is passed through"""
+        from .model import xform
+        euler = np.asarray(euler, dtype=np.float64)
+        return euler if len(euler) == 4 else xform.quat_from_rpy(euler)
 
     def disconnect(self):
         if self._stepper is not None:

@@ -5,8 +5,9 @@
 
 --train runs assistive_gym_amd.ppo.PPOTrainer on --n-envs lock-stepped environments of one GPU, resumes from the newest checkpoint under
 --load-policy-path (learn.py:44-56), prints the line of learn.py:86 per iteration and keeps the newest checkpoint only (learn.py:89-93);
---evaluate prints the statistics of learn.py:172-183.  Flags beyond the reference's: --n-envs, --reset (the vec env's reset mode) and
---deterministic (evaluate with the mean action).  --algo sac and --render are not built and say so.
+--evaluate prints the statistics of learn.py:172-183.  Flags beyond the reference's: --n-envs, --reset (the vec env's reset mode),
+--deterministic (evaluate with the mean action) and --ee-actions (the policy commands end-effector deltas, 6 per arm, turned into joint actions by
+the device-side IK: assistive_gym_amd/ee_control.py; a checkpoint belongs to the action space it was trained in).  --algo sac and --render are not built and say so.
 """
 import argparse
 import os
@@ -32,11 +33,16 @@ def build_parser():
     parser.add_argument('--n-envs', type=int, default=4096, help='Lock-stepped environments on the GPU (default: 4096)')
     parser.add_argument('--reset', default='pool', choices=('pool', 'device', 'host'), help="The batched environment's reset mode (default: pool)")
     parser.add_argument('--deterministic', action='store_true', default=False, help='Evaluate with the mean action instead of a sample')
+    parser.add_argument('--ee-actions', action='store_true', default=False, help='Act in end-effector space: 6 delta components per arm through the device-side IK (default: joint actions)')
     return parser
 
 
-def make_vec_env(env_name, n_envs, seed=1001, reset='pool', device=0):
-    """the batched environment behind a gym id of the reference ('FeedingJaco-v1', 'ScratchItchPR2Human-v1', ...)"""
+def make_vec_env(env_name, n_envs, seed=1001, reset='pool', device=0, ee_actions=False):
+    """the batched environment behind a gym id of the reference ('FeedingJaco-v1', 'ScratchItchPR2Human-v1', ...); ee_actions: wrapped in
+    ee_control.EndEffectorControl (end-effector delta actions)"""
+    if ee_actions:
+        from .ee_control import EndEffectorControl
+        return EndEffectorControl(make_vec_env(env_name, n_envs, seed=seed, reset=reset, device=device))
     from . import vec_env
     from .envs import ENV_IDS
     name = env_name.split(':')[-1]
@@ -52,10 +58,10 @@ def make_vec_env(env_name, n_envs, seed=1001, reset='pool', device=0):
     return cls(n_envs, device=device, seed=seed, reset=reset, coop=coop)
 
 
-def train(env_name, algo, timesteps_total=1000000, save_dir='./trained_models/', load_policy_path='', coop=False, seed=0, n_envs=4096, reset='pool', cfg=None, out=sys.stdout):
+def train(env_name, algo, timesteps_total=1000000, save_dir='./trained_models/', load_policy_path='', coop=False, seed=0, n_envs=4096, reset='pool', cfg=None, out=sys.stdout, ee_actions=False):
     """learn.py:71-94.  Returns (checkpoint path, trainer)."""
     from . import ppo
-    env = make_vec_env(env_name, n_envs, reset=reset)
+    env = make_vec_env(env_name, n_envs, reset=reset, ee_actions=ee_actions)
     trainer = ppo.PPOTrainer(env, cfg or ppo.PPOConfig.batched(n_envs), seed=seed, env_name=env_name)
     checkpoint_path = ppo.latest_checkpoint(load_policy_path, algo, env_name)
     if checkpoint_path is not None:
@@ -74,11 +80,11 @@ def train(env_name, algo, timesteps_total=1000000, save_dir='./trained_models/',
     return checkpoint_path, trainer
 
 
-def evaluate_policy(env_name, algo, policy_path, n_episodes=100, coop=False, seed=0, verbose=False, n_envs=4096, reset='pool', deterministic=False, out=sys.stdout):
+def evaluate_policy(env_name, algo, policy_path, n_episodes=100, coop=False, seed=0, verbose=False, n_envs=4096, reset='pool', deterministic=False, out=sys.stdout, ee_actions=False):
     """learn.py:133-184"""
     from . import ppo
     n_envs = max(1, min(n_envs, n_episodes))
-    env = make_vec_env(env_name, n_envs, seed=1001 + seed, reset=reset)
+    env = make_vec_env(env_name, n_envs, seed=1001 + seed, reset=reset, ee_actions=ee_actions)
     trainer = ppo.PPOTrainer(env, ppo.PPOConfig.batched(n_envs), seed=seed, env_name=env_name)
     path = ppo.latest_checkpoint(policy_path, algo, env_name)
     if path is None:
@@ -110,10 +116,10 @@ def main(argv=None):
     checkpoint_path = None
     if args.train:
         checkpoint_path, _ = train(args.env, args.algo, timesteps_total=args.train_timesteps, save_dir=args.save_dir, load_policy_path=args.load_policy_path, coop=coop,
-                                   seed=args.seed, n_envs=args.n_envs, reset=args.reset)
+                                   seed=args.seed, n_envs=args.n_envs, reset=args.reset, ee_actions=args.ee_actions)
     if args.evaluate:
         evaluate_policy(args.env, args.algo, checkpoint_path if checkpoint_path is not None else args.load_policy_path, n_episodes=args.eval_episodes, coop=coop,
-                        seed=args.seed, verbose=args.verbose, n_envs=args.n_envs, reset=args.reset, deterministic=args.deterministic)
+                        seed=args.seed, verbose=args.verbose, n_envs=args.n_envs, reset=args.reset, deterministic=args.deterministic, ee_actions=args.ee_actions)
     return 0
 
 

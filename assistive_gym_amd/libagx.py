@@ -15,7 +15,7 @@ EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_p
            'agx_set_state', 'agx_get_state', 'agx_state_dev', 'agx_settle', 'agx_settle_debug', 'agx_cloth_nodes', 'agx_set_cloth', 'agx_get_cloth', 'agx_cloth_dev', 'agx_set_cloth_pool', 'agx_get_cloth_report', 'agx_step', 'agx_step_debug', 'agx_step_timed', 'agx_debug_words',
            'agx_observe', 'agx_observe_masked', 'agx_reset_done_at', 'agx_sample_reset', 'agx_reset', 'agx_attach_settle_model', 'agx_reset_done', 'agx_step_host', 'agx_observe_host', 'agx_profile_begin', 'agx_profile_end',
            'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_chunk_count', 'agx_set_env_offset', 'agx_check_collisions',
-           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae']
+           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae', 'agx_ee_arms', 'agx_ee_pose', 'agx_ee_ik']
 
 
 class AgxError(RuntimeError):
@@ -34,6 +34,9 @@ def load():
         L.agx_policy_act.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_longlong, C.c_uint32, C.c_int,
                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.agx_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.agx_ee_arms.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.agx_ee_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.agx_ee_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -230,6 +233,29 @@ class Stepper:
         v = _View()
         v.__cuda_array_interface__ = dict(shape=(self.n_envs, 2, self.cloth_nodes(), 3), typestr='<f4', data=(p.value, False), version=2, strides=None)
         return torch.as_tensor(v, device='cuda:%d' % self.device)
+
+    # ---- end-effector control (agx_ee_arms / agx_ee_pose / agx_ee_ik, include/agx.h)
+    EE_FRAMES = {'absolute': 0, 'delta': 1}       # AGX_EE_ABSOLUTE, AGX_EE_DELTA
+
+    def ee_arms(self):
+        """arm chains end-effector control serves: 1, 2 for a two-armed robot in arm manipulation, 0 for a robot on wheels"""
+        out = C.c_int()
+        check(self.L.agx_ee_arms(self.h, C.byref(out)), 'agx_ee_arms')
+        return out.value
+
+    def ee_pose(self, out, stream=0):
+        """out: contiguous float32 device tensor [n_envs, arms, 7] <- world position and quaternion (x, y, z, w) of every end-effector frame"""
+        assert out.is_contiguous() and out.numel() == self.n_envs * max(1, self.ee_arms()) * 7
+        check(self.L.agx_ee_pose(self.h, out.data_ptr(), stream or None), 'agx_ee_pose')
+
+    def ee_ik(self, target, frame='delta', iters=8, damping=0.05, gain=10.0, q_out=None, action=None, err=None, stream=0):
+        """agx_ee_ik.  target: float32 device tensor whose rows are the environments (a column slice of a wider tensor is fine: its row stride is
+        passed on), per arm 7 floats ('absolute') or 6 ('delta'); q_out [n_envs, arms, 7], err [n_envs, arms, 2]: contiguous, optional; action:
+        optional [n_envs, >= act_dim] rows -- only the columns of the arm chains are written"""
+        assert target.stride(-1) == 1 and all(x is None or x.is_contiguous() for x in (q_out, err)) and (action is None or action.stride(-1) == 1)
+        check(self.L.agx_ee_ik(self.h, target.data_ptr(), target.stride(0), self.EE_FRAMES[frame], int(iters), float(damping), float(gain),
+                               q_out.data_ptr() if q_out is not None else None, action.data_ptr() if action is not None else None,
+                               action.stride(0) if action is not None else 0, err.data_ptr() if err is not None else None, stream or None), 'agx_ee_ik')
 
     def settle(self, n_substeps, stream=0):
         check(self.L.agx_settle(self.h, C.c_int(n_substeps), C.c_void_p(stream)), 'agx_settle')

@@ -200,6 +200,37 @@ int agx_policy_act(const float* params_dev, int obs_dim, int hidden_a, int hidde
 int agx_gae(const float* rewards_dev, const float* values_dev, const uint8_t* dones_dev, int horizon, int n_envs,
             float gamma, float lam, float* adv_dev, float* ret_dev, void* stream);
 
+/* ---- end-effector control: Cartesian commands for the arm(s), turned into joint-space actions on the device (csrc/agx_ik.h, csrc/agx_ik.hip).
+ * The reference's teleop_example.py / igibson_drinking_example.py read robot.get_pos_orient(robot.right_end_effector), call robot.ik(...) on a
+ * target pose and send (target_joint_angles - current_joint_angles) * 10 as the action; these entries do the same for every environment of a
+ * handle.  The IK is the damped-least-squares iteration of assistive_gym_amd/host/kin.py (RobotKin.ik) in float32 -- Bullet's own IK is not
+ * reproduced anywhere in this project.  Nothing here writes the state records.
+ *
+ * agx_ee_arms: arm chains the handle's model has -- 1, 2 for a two-armed robot in arm manipulation (AGX_X_CHAIN2: index 0 = the right arm, 1 =
+ * the left), 0 for a robot on wheels (AGX_H_BASE_LINK > 0) and for any blob whose chain is not the serial 7-joint arm agx_create checks for its
+ * reset generator.  With 0 arms the two entries below return AGX_E_ARG.
+ * agx_ee_pose: pose_dev[n_envs][arms][7] = world position and quaternion (x, y, z, w) of the end-effector frame (AGX_T_EE_*, AGX_T_EE2_*).
+ * agx_ee_ik: target_dev rows of target_stride floats, per arm 7 floats (frame AGX_EE_ABSOLUTE: world position, quaternion x y z w, normalised on the
+ * device) or 6 (AGX_EE_DELTA: world translation d and world rotation vector r applied to the current pose: p + d, exp(r) (x) q).  `iters`
+ * iterations (1..1000) from the state's joint angles: e = [dp; 2 vec(q_t (x) conj(q))] with the quaternion flipped to w >= 0,
+ * dq = J^T (J J^T + damping^2 I)^-1 e, the whole step scaled down to max|dq| <= 0.5, q clipped to [AGX_R_LOWER, AGX_R_UPPER]; an
+ * environment stops once both error norms are below 1e-4.  Outputs, each may be NULL: q_out_dev[n_envs][arms][7] joint angles; err_dev[n_envs][arms][2]
+ * position and orientation error norms at exit; action_dev rows of action_stride floats (>= the action dimension): every chain joint's action
+ * column (AGX_R_ACT, and the duplicate column of a single arm driven as 'both', AGX_T_DUP_ACT) = gain (q_out - q), the columns of one arm scaled
+ * together so that the largest magnitude is at most 1 (the direction survives where the environment's own clip would bend it).  Columns of no
+ * chain -- the human's in a co-op batch -- are not touched.  A state or a target that is not finite: action 0, err +inf, q_out = q; a
+ * non-finite action is never written.
+ * AGX_E_ARG with agx_last_error text, before any launch: NULL handle, NULL target, 0 arms, iters outside 1..1000, damping <= 0, target_stride <
+ * arms x 7 (6), action_stride < the action dimension, an unknown frame. */
+#ifndef AGX_EE_FRAMES
+#define AGX_EE_FRAMES
+enum { AGX_EE_ABSOLUTE = 0, AGX_EE_DELTA = 1 };
+#endif
+int agx_ee_arms(agx_handle h, int* arms);
+int agx_ee_pose(agx_handle h, float* pose_dev, void* stream);
+int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int frame, int iters, float damping, float gain,
+              float* q_out_dev, float* action_dev, int action_stride, float* err_dev, void* stream);
+
 /* convenience wrappers with HOST buffers (copies included; not the timed path) */
 int agx_step_host(agx_handle h, const float* actions, float* obs, float* reward, uint8_t* done, float* info);
 int agx_observe_host(agx_handle h, float* obs);
