@@ -15,6 +15,7 @@ CPU fallback, constructing the env without a GPU raises.
 import numpy as np
 
 from .blob import ModelBlob
+from .reset_recipes import SETTLE_STEPS, HostSampler, sample_on_device      # noqa: F401 (SETTLE_STEPS: the feeding row's, as this module always exported it)
 
 try:                                     # gym is optional here (not installed in the build image)
     import gym
@@ -52,8 +53,6 @@ except Exception:                        # minimal stand-ins with the attributes
 
     class _Base:
         metadata = {}
-
-SETTLE_STEPS = 25       # feeding.py:178-179
 
 
 def _box(n, bound):
@@ -174,7 +173,7 @@ class AssistiveEnv(_Base):
         self.iteration = 0
         self.task_success = 0
         self.total_force_on_human = 0.0
-        self._stepper = None
+        self._stepper, self._host_sampler = None, None
         arm_pb = [base.robot_i(d, 'PB_INDEX') for d in sorted((d for d in range(base.nrobot) if base.robot_i(d, 'ACT') >= 0 and base.robot_i(d, 'ACT_SRC') == 0), key=lambda d: base.robot_i(d, 'ACT'))]
         if base.act_dim_robot == 2 * len(arm_pb):                                     # a single-arm robot with robot_arm = 'both' (robot.py:16)
             arm_pb = arm_pb + arm_pb
@@ -209,8 +208,24 @@ class AssistiveEnv(_Base):
         draw = r.integers if hasattr(r, 'integers') else r.randint
         return (int(draw(0, 2 ** 31 - 1)) << 31) | int(draw(0, 2 ** 31 - 1))
 
+    sampler = 'host'          # where reset() is sampled: 'device' (the reset generator, csrc/agx_reset.h) or 'host' (the numpy sampler under host/)
+
     def reset(self):
-        raise NotImplementedError('Implement reset')                                              # env.py:69-70
+        """<Task>Env.reset by the task's recipe (reset_recipes.py), as vec_env.build_reset_pool builds one pool entry.  'device': sampled by
+        the reset generator (human, IK restarts with collision rejection, tool, targets), then the recipe's settle steps.  'host': the draws,
+        the base pose search and the IK restated in numpy (host/) around the settles of the recipe, which run on the device (the rag doll on
+        the bed_settle model, the arm's fall, the garment's 50 steps), with the device's collision pass rejecting colliding placements; the
+        result is injected into the stepper."""
+        st = self._ensure_stepper()
+        self.reset_seed = self._draw_seed()
+        if self.sampler == 'device':
+            sample_on_device(st, self.blob, self.reset_seed, 'random', fused=False)
+        else:
+            if self._host_sampler is None:
+                self._host_sampler = HostSampler(self.blob, 1, self.device)
+            self._host_sampler.inject(st, *self._host_sampler(1, self.reset_seed % (2 ** 31)))
+        self.iteration, self.task_success = 0, 0
+        return self._split_obs(st.observe_host()[0].astype(np.float64))
 
     def _split_obs(self, obs):
         if not self.coop:
@@ -279,17 +294,7 @@ class AssistiveEnv(_Base):
 
 class FeedingJacoEnv(AssistiveEnv):
     """FeedingJaco-v1: Jaco arm on a wheelchair feeds a static (non-cooperating) human."""
-    model, task = 'feeding_jaco', 'feeding'
-
-    def reset(self):
-        """FeedingEnv.reset (feeding.py:114-182): sampled on the device (agx_sample_reset: human, IK with random
-        restarts, tool / bowl / food), settled for 25 substeps, observed."""
-        st = self._ensure_stepper()
-        self.reset_seed = self._draw_seed()
-        st.sample_reset(self.reset_seed, impairment='random')
-        st.settle(SETTLE_STEPS)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
+    model, task, sampler = 'feeding_jaco', 'feeding', 'device'
 
 
 class FeedingJacoHumanEnv(FeedingJacoEnv):
@@ -301,20 +306,7 @@ class FeedingJacoHumanEnv(FeedingJacoEnv):
 class FeedingSawyerEnv(FeedingJacoEnv):
     """FeedingSawyer-v1 (feeding_envs.py:25-27): a free-standing robot; its base pose comes from the base pose search on the host
     (host/reset.py + host/reset_bed.py) with the device's collision pass rejecting colliding placements, then the 25 settle steps."""
-    model = 'feeding_sawyer'
-
-    def reset(self):
-        from .host.reset import make_states
-        from .host.reset_bed import DeviceCollisionChecker
-        st = self._ensure_stepper()
-        if not hasattr(self, '_checker'):
-            self._checker = DeviceCollisionChecker(self.blob, 1, self.device)
-        self.reset_seed = self._draw_seed()
-        rec, _ = make_states(self.blob, 1, seed=self.reset_seed % (2 ** 31), checker=self._checker)
-        st.set_state(rec)
-        st.settle(SETTLE_STEPS)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
+    model, sampler = 'feeding_sawyer', 'host'
 
 
 class FeedingSawyerHumanEnv(FeedingSawyerEnv):
@@ -342,32 +334,25 @@ class FeedingPandaHumanEnv(FeedingPandaEnv):
     coop = True
 
 
-class DrinkingJacoEnv(AssistiveEnv):
-    """DrinkingJaco-v1 (drinking_envs.py:29-31): the wheelchair-mounted Jaco tilts a cup with 64 water particles at the person's mouth.
-    The water lives next to the state record on the device (float32 [2, 64, 3]: positions, velocities)."""
-    model, task = 'drinking_jaco', 'drinking'
+class _PairState:
+    """the garment / the water lives outside the state record: a state is the pair (record, array[2][nodes][3])"""
 
-    def reset(self):
-        """DrinkingEnv.reset (drinking.py:122-181) on the device: human, target, robot start pose (IK restarts / base pose search / placement
-        draws with collision rejection), cup, the 4 x 4 x 4 water grid above it, then the 50 steps in which the water drops into the cup"""
-        st = self._ensure_stepper()
-        self.reset_seed = self._draw_seed()
-        st.sample_reset(self.reset_seed, impairment='random')
-        st.settle(50)                                                                              # drinking.py:176-177
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
-
-    # the water lives outside the state record: a state is the pair (record, water[2][64][3])
     def get_state(self):
         st = self._ensure_stepper()
         return st.get_state()[0], st.get_cloth()[0]
 
     def set_state(self, state):
         if not (isinstance(state, (tuple, list)) and len(state) == 2):
-            raise ValueError('a drinking state is the pair (state record, water): pass what get_state() returned')
+            raise ValueError('a %s state is the pair (state record, %s): pass what get_state() returned' % (self.task, 'water' if self.task == 'drinking' else 'garment'))
         st = self._ensure_stepper()
         st.set_state(np.asarray(state[0], dtype=np.float32).reshape(1, -1))
         st.set_cloth(np.ascontiguousarray(state[1], dtype=np.float32)[None])
+
+
+class DrinkingJacoEnv(_PairState, AssistiveEnv):
+    """DrinkingJaco-v1 (drinking_envs.py:29-31): the wheelchair-mounted Jaco tilts a cup with 64 water particles at the person's mouth.
+    The water lives next to the state record on the device (float32 [2, 64, 3]: positions, velocities)."""
+    model, task, sampler = 'drinking_jaco', 'drinking', 'device'
 
 
 class DrinkingJacoHumanEnv(DrinkingJacoEnv):
@@ -378,20 +363,6 @@ class DrinkingJacoHumanEnv(DrinkingJacoEnv):
 class BedBathingSawyerEnv(AssistiveEnv):
     """BedBathingSawyer-v1 (bed_bathing_envs.py:23-25): Sawyer wipes the right arm of a human lying on a bed."""
     model, task = 'bed_bathing_sawyer', 'bed_bathing'
-
-    def reset(self):
-        """BedBathingEnv.reset (bed_bathing.py:112-171): the draws, the TOC base pose search and the IK restated on the host
-        (host/reset_bed.py) around the rag-doll settle of the human, which runs on the device (bed_settle model); the result is
-        injected into the stepper."""
-        from .host.reset_bed import make_states, RagdollSettler, DeviceCollisionChecker
-        st = self._ensure_stepper()
-        if not hasattr(self, '_settler'):
-            self._settler, self._checker = RagdollSettler(1, self.device), DeviceCollisionChecker(self.blob, 1, self.device)
-        self.reset_seed = self._draw_seed()
-        rec, _ = make_states(self.blob, 1, seed=self.reset_seed % (2 ** 31), settler=self._settler, checker=self._checker)
-        st.set_state(rec)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
 
 
 class BedBathingSawyerHumanEnv(BedBathingSawyerEnv):
@@ -404,19 +375,6 @@ class ScratchItchPR2Env(AssistiveEnv):
     """ScratchItchPR2-v1 (scratch_itch_envs.py:17-19): the PR2's left arm scratches a target on the seated human's right arm."""
     model, task = 'scratch_itch_pr2', 'scratch_itch'
 
-    def reset(self):
-        """ScratchItchEnv.reset (scratch_itch.py:93-132), restated on the host (host/reset_scratch.py); its result is injected."""
-        from .host.reset_scratch import make_states
-        from .host.reset_bed import DeviceCollisionChecker
-        st = self._ensure_stepper()
-        if not hasattr(self, '_checker'):
-            self._checker = DeviceCollisionChecker(self.blob, 1, self.device)
-        self.reset_seed = self._draw_seed()
-        rec, _ = make_states(self.blob, 1, seed=self.reset_seed % (2 ** 31), checker=self._checker)
-        st.set_state(rec)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
-
 
 class ScratchItchPR2HumanEnv(ScratchItchPR2Env):
     """ScratchItchPR2Human-v1 (scratch_itch_envs.py:41-44; BASELINE config 4): the human's right arm (10 joints) is controllable,
@@ -428,14 +386,7 @@ class ScratchItchJacoEnv(ScratchItchPR2Env):
     """ScratchItchJaco-v1 (scratch_itch_envs.py:29-31; the default environment of the reference's env_viewer.py / learn.py): the
     wheelchair-mounted Jaco holds the scratcher.  reset() is sampled on the device (agx_sample_reset: human, IK with random restarts and
     collision rejection, tool, target on the arm), as FeedingJacoEnv's."""
-    model = 'scratch_itch_jaco'
-
-    def reset(self):
-        st = self._ensure_stepper()
-        self.reset_seed = self._draw_seed()
-        st.sample_reset(self.reset_seed, impairment='random')
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
+    model, sampler = 'scratch_itch_jaco', 'device'
 
 
 class ScratchItchJacoHumanEnv(ScratchItchJacoEnv):
@@ -460,37 +411,10 @@ class ScratchItchSawyerHumanEnv(ScratchItchSawyerEnv):
     coop = True
 
 
-class DressingBaxterEnv(AssistiveEnv):
+class DressingBaxterEnv(_PairState, AssistiveEnv):
     """DressingBaxter-v1 (dressing_envs.py:19-21; BASELINE config 5): Baxter's left arm pulls the sleeve of a hospital gown over the left
     arm of the seated human.  The garment (3,966 nodes) lives next to the state record on the device."""
     model, task = 'dressing_baxter', 'dressing'
-
-    def reset(self):
-        """DressingEnv.reset (dressing.py:112-198): the draws, the TOC base pose search and the IK restated on the host
-        (host/reset_dressing.py); the garment is loaded relative to the end effector and settles for 50 steps on the device."""
-        from .host.reset_dressing import make_states, ClothSettler
-        from .host.reset_bed import DeviceCollisionChecker
-        st = self._ensure_stepper()
-        if not hasattr(self, '_settler'):
-            self._settler, self._checker = ClothSettler(self.blob, 1, self.device), DeviceCollisionChecker(self.blob, 1, self.device)
-        self.reset_seed = self._draw_seed()
-        rec, cloth, _ = make_states(self.blob, 1, seed=self.reset_seed % (2 ** 31), settler=self._settler, checker=self._checker)
-        st.set_state(rec)
-        st.set_cloth(cloth)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
-
-    # the garment lives outside the state record: a state is the pair (record, garment[2][NN][3])
-    def get_state(self):
-        st = self._ensure_stepper()
-        return st.get_state()[0], st.get_cloth()[0]
-
-    def set_state(self, state):
-        if not (isinstance(state, (tuple, list)) and len(state) == 2):
-            raise ValueError('a dressing state is the pair (state record, garment): pass what get_state() returned')
-        st = self._ensure_stepper()
-        st.set_state(np.asarray(state[0], dtype=np.float32).reshape(1, -1))
-        st.set_cloth(np.ascontiguousarray(state[1], dtype=np.float32)[None])
 
 
 class DressingBaxterHumanEnv(DressingBaxterEnv):
@@ -503,20 +427,6 @@ class ArmManipulationSawyerEnv(AssistiveEnv):
     """ArmManipulationSawyer-v1 (arm_manipulation_envs.py:23-25): Sawyer lifts the limp right arm of a human lying on a bed back onto
     the body with a scooper.  robot_arm = 'both' on a single-arm robot: 14 actions (the arm joints twice, robot.py:16)."""
     model, task = 'arm_manipulation_sawyer', 'arm_manipulation'
-
-    def reset(self):
-        """ArmManipulationEnv.reset (arm_manipulation.py:110-182): host/reset_arm.py around the two settles on the device."""
-        from .host.reset_arm import make_states, ArmFallSettler
-        from .host.reset_bed import RagdollSettler, DeviceCollisionChecker
-        st = self._ensure_stepper()
-        if not hasattr(self, '_settler'):
-            self._settler, self._arm_settler = RagdollSettler(1, self.device), ArmFallSettler(self.blob, 1, self.device)
-            self._checker = DeviceCollisionChecker(self.blob, 1, self.device)
-        self.reset_seed = self._draw_seed()
-        rec, _ = make_states(self.blob, 1, seed=self.reset_seed % (2 ** 31), settler=self._settler, arm_settler=self._arm_settler, checker=self._checker)
-        st.set_state(rec)
-        self.iteration, self.task_success = 0, 0
-        return self._split_obs(st.observe_host()[0].astype(np.float64))
 
 
 class ArmManipulationSawyerHumanEnv(ArmManipulationSawyerEnv):
@@ -550,7 +460,6 @@ _robot_flavours(ArmManipulationSawyerEnv, 'ArmManipulation', [('Jaco', 'arm_mani
 _robot_flavours(ScratchItchPR2Env, 'ScratchItch', [('Baxter', 'scratch_itch_baxter'), ('Stretch', 'scratch_itch_stretch')], 'scratch_itch_envs.py:21-23,31-33,46-50,58-62')
 _robot_flavours(DrinkingJacoEnv, 'Drinking', [('PR2', 'drinking_pr2'), ('Baxter', 'drinking_baxter'), ('Sawyer', 'drinking_sawyer'), ('Stretch', 'drinking_stretch'), ('Panda', 'drinking_panda')],
                 'drinking_envs.py:15-27,33-55,61-67')
-
 
 
 def make(env_id):

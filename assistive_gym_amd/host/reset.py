@@ -1,6 +1,6 @@
 """Host-side reset for the feeding task (FeedingJaco-v1 and the other robots of model/compiler.py FEEDING_ROBOTS): produces the
 pre-settle state record of one environment.  Wheelchair-mounted robots (Jaco, Panda) get Robot.ik_random_restarts from their fixed base;
-free-standing ones (Sawyer, Baxter) the base pose search of Robot.position_robot_toc (host/reset_bed.py) with the goals
+free-standing ones (Sawyer, Baxter) the base pose search of Robot.position_robot_toc (host/base_pose.py) with the goals
 [(target_ee_pos, target_ee_orient)] + [(mouth, None)] (feeding.py:141).
 
 Follows the order of FeedingEnv.reset (assistive_gym/envs/feeding.py:114-182) and what it calls:
@@ -24,7 +24,8 @@ rejection of robot.py:105-112 / env.py:299-308: it has no narrowphase of its own
 import numpy as np
 
 from ..model import xform as X
-from ..model.human import HumanModel
+from .common import (IDENTITY, draw_human, human_model, seated_base, write_human_frames, open_gripper, write_joints, frozen_unless_agent, tool_com_pose,
+                     write_env_tail, placement_rng, sample_batch)
 from .kin import RobotKin
 
 D = np.deg2rad
@@ -54,7 +55,35 @@ class MobilePlacement:
         return pos, X.quat_from_rpy(rpy), q
 
 
+def ik_random_restarts(rng, kin, base_pos, base_quat, target_pos, target_quat, max_restarts=1000):
+    """Robot.ik_random_restarts (robot.py:84-121) from a fixed base: a random rest pose per restart (the limits randomised after the tenth),
+    until the end effector is within 0.01 of the target pose -> (joint vector: the closest one when none qualifies, |position error|, ok, restarts)"""
+    ik_lo = np.where(kin.lower < -1e9, -2 * np.pi, kin.lower)                  # agent.py:223-231
+    ik_hi = np.where(kin.upper > 1e9, 2 * np.pi, kin.upper)
+    best, best_d, ok, restarts = np.clip(np.zeros(kin.n), kin.lower, kin.upper), np.inf, False, 0      # Agent.init -> enforce_joint_limits
+    for r in range(max_restarts):
+        restarts = r + 1
+        lo, hi = ik_lo, ik_hi
+        if r >= 10:                                                            # robot.py:91 randomize_limits
+            lo = rng.uniform(0, 1, size=kin.n) * ik_lo
+            hi = rng.uniform(0, 1, size=kin.n) * ik_hi
+        rest = rng.uniform(lo, hi)                                             # agent.py:263
+        qs = kin.ik(base_pos, base_quat, rest, target_pos, target_quat, lower=np.minimum(lo, hi), upper=np.maximum(lo, hi))
+        qs = np.clip(qs, kin.lower, kin.upper)                                 # set_joint_angles(use_limits=True)
+        p, o = kin.ee_pose(base_pos, base_quat, qs)
+        dpos = np.linalg.norm(target_pos - p)
+        dor = min(np.linalg.norm(target_quat - o), np.linalg.norm(target_quat + o))
+        if dpos < best_d:
+            best, best_d = qs, dpos
+        if dpos < 0.01 and dor < 0.01:                                         # robot.py:97 success_threshold
+            best, ok = qs, True
+            break
+    return best, best_d, ok, restarts
+
+
 class FeedingJacoReset:
+    HEAD_PRESET = [(6, -90), (16, -90), (28, -90), (31, 80), (35, -90), (38, 80)]      # feeding.py:124, drinking.py:132
+
     def __init__(self, blob):
         self.blob = blob
         self.kin = RobotKin(blob)
@@ -68,127 +97,64 @@ class FeedingJacoReset:
             from .reset_bed import toc_search
             self.toc = toc_search(blob)
         self.mobile = MobilePlacement(blob) if blob.meta.get('mount') == 'mobile' else None
-        self._hm_cache = {}
 
-    def _human(self, gender, limit_scale):
-        key = (gender, round(float(limit_scale), 9))
-        if key not in self._hm_cache:
-            if len(self._hm_cache) > 64:
-                self._hm_cache.clear()
-            self._hm_cache[key] = HumanModel(gender, limit_scale)
-        return self._hm_cache[key]
+    def seated_human(self, rng, v, impairment, gender):
+        """the draws of build_assistive_env, the seated human with its head angles ~ U(-30, 30)^3 degrees (feeding.py:124-125, drinking.py:132-133),
+        its frames in the record, the target at its mouth (feeding.py:184-196) -> (draw, joint angles, target)"""
+        b = self.blob
+        draw = draw_human(rng, impairment, gender, 4, 20)                          # human.py:89-90 (head joints)
+        hm = human_model(draw.gender, draw.limit_scale)
+        hq = hm.clamp(np.zeros(hm.n))                                              # human_creation.py:301-314
+        for j, a in self.HEAD_PRESET + [(21, rng.uniform(-30, 30)), (22, rng.uniform(-30, 30)), (23, rng.uniform(-30, 30))]:
+            hq[j] = D(a)
+        hq = hm.clamp(hq)                                                          # set_joint_angles(use_limits) + enforce_joint_limits
+        hbase = seated_base(draw.gender)
+        hpos, hquat = hm.fk(hbase, IDENTITY, hq)
+        write_human_frames(v, self.human_bodies, hpos, hquat, hbase, [0, 0, 0, 1])
+        mouth = b.task_f('MOUTH_M' if draw.gender == 'male' else 'MOUTH_F', 3)
+        target, _ = X.compose(hpos[23], hquat[23], mouth, IDENTITY)
+        return draw, hq, target
+
+    def write_arm_and_head(self, v, draw, hq, q, base_pos, base_quat):
+        """gripper, joints (the head: dynamic links, frozen unless the impairment is tremor or the human controllable), the tool in the gripper
+        (tool.py:49-62) -> the tool's position"""
+        b = self.blob
+        open_gripper(b, q)
+        write_joints(v, b, q, np.array([hq[j] for j in self.human_dyn]), draw, frozen_unless_agent(b, draw), base_pos, base_quat)
+        tp, tq = self.kin.tool_pose(base_pos, base_quat, q)
+        free = v['free'][0]
+        free[:] = 0
+        free[:, 6] = 1.0
+        free[b.h['TOOL_BODY'], :3], free[b.h['TOOL_BODY'], 3:7] = tp, tq
+        return tp
 
     def sample(self, rng, state_row, env_seed=0, impairment='random', gender='random', max_restarts=1000, info=None, attempt=0):
         """Fill one state record (float32 view of length state_words) in place.  attempt > 0 (free-standing robots): a re-draw of the
         robot's placement only (init_robot_pose's rejection loop, env.py:281-308)."""
         b, kin = self.blob, self.kin
         v = b.view(state_row)
-        plane_friction = rng.uniform(0.025, 0.5)                                   # env.py:120
-        if gender not in ('male', 'female'):
-            gender = rng.choice(['male', 'female'])                                # human.py:76-77
-        if impairment == 'random':
-            impairment = rng.choice(['none', 'limits', 'weakness', 'tremor'])      # human.py:80-81
-        elif impairment == 'no_tremor':
-            impairment = rng.choice(['none', 'limits', 'weakness'])
-        limit_scale = 1.0 if impairment != 'limits' else rng.uniform(0.5, 1.0)     # human.py:85
-        strength = 1.0 if impairment != 'weakness' else rng.uniform(0.25, 1.0)     # human.py:86
-        tremors = np.zeros(4)
-        if impairment == 'tremor':
-            tremors = rng.uniform(D(-20), D(20), size=4)                           # human.py:89-90 (head joints)
-        rng.uniform(0.4, 0.8)                                                      # skin colour, human_creation.py:63
-        hm = self._human(gender, limit_scale)
-        hq = hm.clamp(np.zeros(hm.n))                                              # human_creation.py:301-314
-        jp = [(6, -90), (16, -90), (28, -90), (31, 80), (35, -90), (38, 80),       # feeding.py:124
-              (21, rng.uniform(-30, 30)), (22, rng.uniform(-30, 30)), (23, rng.uniform(-30, 30))]   # feeding.py:125
-        for j, a in jp:
-            hq[j] = D(a)
-        hq = hm.clamp(hq)                                                          # set_joint_angles(use_limits) + enforce_joint_limits
-        hbase = np.array([0, 0.03, 0.89 if gender == 'male' else 0.86])            # human.py:102
-        hpos, hquat = hm.fk(hbase, np.array([0, 0, 0, 1.0]), hq)
-        for k, link in enumerate(self.human_bodies):
-            if link < 0:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = hbase, [0, 0, 0, 1]
-            else:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = hpos[link], hquat[link]
-        mouth = b.task_f('MOUTH_M' if gender == 'male' else 'MOUTH_F', 3)
-        target, _ = X.compose(hpos[23], hquat[23], mouth, np.array([0, 0, 0, 1.0]))   # feeding.py:184-196
+        draw, hq, target = self.seated_human(rng, v, impairment, gender)
         # robot start pose: IK with random restarts towards a point in front of the person
         target_ee_pos = np.array([-0.15, -0.65, 1.15]) + rng.uniform(-0.05, 0.05, size=3)      # feeding.py:139
-        q = np.clip(np.zeros(kin.n), kin.lower, kin.upper)                         # Agent.init -> enforce_joint_limits
-        ik_lo = np.where(kin.lower < -1e9, -2 * np.pi, kin.lower)                  # agent.py:223-231
-        ik_hi = np.where(kin.upper > 1e9, 2 * np.pi, kin.upper)
-        best, best_d, ok, restarts = None, np.inf, False, 0
-        base_pos, base_quat = self.base_pos, self.base_quat
-        if b.meta.get('mount') == 'mobile':
-            # a robot on wheels (MobilePlacement).  attempt > 0: init_robot_pose's re-draw after a collision (env.py:299-308)
-            from .reset_bed import placement_rng
+        base_pos, base_quat, ok, restarts = self.base_pos, self.base_quat, True, 0
+        if self.mobile is not None or self.toc is not None:
+            # a robot on wheels (MobilePlacement) or a free-standing one (base pose search).  attempt > 0: init_robot_pose's re-draw after a collision (env.py:299-308)
             prng = placement_rng(np.random.RandomState(rng.randint(1 << 31)), env_seed, attempt)
-            base_pos, base_quat, best = self.mobile.draw(prng)
-            p, o = kin.ee_pose(base_pos, base_quat, best)
-            best_d, ok, max_restarts = float(np.linalg.norm(target_ee_pos - p)), True, 0
-        elif self.toc is not None:
-            from .reset_bed import placement_rng
-            prng = placement_rng(np.random.RandomState(rng.randint(1 << 31)), env_seed, attempt)
-            res = None
-            for _ in range(4):
-                res = self.toc._toc(prng, target_ee_pos, [target])
-                if res is not None:
-                    break
-            assert res is not None, 'no reachable base pose found'
-            base_pos, base_quat, q_arm, ngoal, manip = res
-            best = q.copy()
-            for k_, d_ in enumerate(self.toc.arm.chain):
-                best[d_] = q_arm[k_]
-            p, o = kin.ee_pose(base_pos, base_quat, best)
-            best_d, ok, max_restarts = float(np.linalg.norm(target_ee_pos - p)), True, 0
-        for r in range(max_restarts):
-            restarts = r + 1
-            lo, hi = ik_lo, ik_hi
-            if r >= 10:                                                            # robot.py:91 randomize_limits
-                lo = rng.uniform(0, 1, size=kin.n) * ik_lo
-                hi = rng.uniform(0, 1, size=kin.n) * ik_hi
-            rest = rng.uniform(lo, hi)                                             # agent.py:263
-            qs = kin.ik(self.base_pos, self.base_quat, rest, target_ee_pos, self.toc_ee_orient,
-                        lower=np.minimum(lo, hi), upper=np.maximum(lo, hi))
-            qs = np.clip(qs, kin.lower, kin.upper)                                 # set_joint_angles(use_limits=True)
-            p, o = kin.ee_pose(self.base_pos, self.base_quat, qs)
-            dpos = np.linalg.norm(target_ee_pos - p)
-            dor = min(np.linalg.norm(self.toc_ee_orient - o), np.linalg.norm(self.toc_ee_orient + o))
-            if dpos < best_d:
-                best, best_d = qs, dpos
-            if dpos < 0.01 and dor < 0.01:                                         # robot.py:97 success_threshold
-                best, ok = qs, True
-                break
-        q = best.copy()
-        for d in range(kin.n):                                                     # gripper, feeding.py:144 (set instantly)
-            if kin.act[d] < 0:
-                q[d] = min(max(b.robot_f(d, 'QT0'), kin.lower[d]), kin.upper[d])
-        nr = b.nrobot
-        v['q'][0, :nr] = q
-        v['qd'][0] = 0
-        v['qt'][0, :nr] = q       # motors hold the start pose until the first action (see module docstring)
-        # human head joints: dynamic links, frozen (mass 0, human.py:104-110) unless the impairment is tremor
-        hq_dyn = np.array([hq[j] for j in self.human_dyn])
-        v['q'][0, nr:] = hq_dyn
-        v['qt'][0, nr:] = hq_dyn
-        v['tremor'][0] = tremors
-        v['tremor_target'][0] = hq_dyn                                             # human.py:123 target_joint_angles
-        # a controllable human keeps its controllable joints dynamic (human.py:108)
-        v['frozen'][0] = 0 if (impairment == 'tremor' or b.is_coop) else (((1 << b.nhdof) - 1) << nr)
-        v['limit_scale'][0] = limit_scale
-        v['base'][0, :3], v['base'][0, 3:] = base_pos, base_quat
-        # tool in the gripper (tool.py:49-62)
-        tp, tq = kin.tool_pose(base_pos, base_quat, q)
+            if self.mobile is not None:
+                base_pos, base_quat, q = self.mobile.draw(prng)
+            else:
+                base_pos, base_quat, q_arm, _, _ = self.toc.search(prng, target_ee_pos, [target])
+                q = np.clip(np.zeros(kin.n), kin.lower, kin.upper)                 # Agent.init -> enforce_joint_limits
+                q[self.toc.arm.chain] = q_arm
+            best_d = float(np.linalg.norm(target_ee_pos - kin.ee_pose(base_pos, base_quat, q)[0]))
+        else:
+            q, best_d, ok, restarts = ik_random_restarts(rng, kin, base_pos, base_quat, target_ee_pos, self.toc_ee_orient, max_restarts)
+        q = q.copy()
+        tp = self.write_arm_and_head(v, draw, hq, q, base_pos, base_quat)          # gripper: feeding.py:144
         free = v['free'][0]
-        free[:] = 0
-        free[:, 6] = 1.0
-        free[b.h['TOOL_BODY'], :3], free[b.h['TOOL_BODY'], 3:7] = tp, tq
         # bowl on the table (furniture.py:32-34); URDF base frame -> COM frame
         bowl_base = np.array([-0.15, -0.65, 0.75]) + np.array([rng.uniform(-0.05, 0.05), rng.uniform(-0.05, 0.05), 0])
-        refp, refq = b.free_f(1, 'REFPOS', 3), b.free_f(1, 'REFQUAT', 4)
-        ip, iq = X.invert(refp, refq)
-        cp, cq = X.compose(bowl_base, np.array([0, 0, 0, 1.0]), ip, iq)
-        free[1, :3], free[1, 3:7] = cp, cq
+        free[1, :3], free[1, 3:7] = tool_com_pose(b, 1, bowl_base, IDENTITY)
         # food grid above the spoon (feeding.py:158-166)
         r_food, k = 0.005, 0
         for i in range(2):
@@ -196,18 +162,12 @@ class FeedingJacoReset:
                 for kk in range(2):
                     free[b.h['FOOD0'] + k, :3] = np.array([i * 2 * r_food - 0.005, j * 2 * r_food, kk * 2 * r_food + 0.01]) + tp
                     k += 1
-        v['plane_friction'][0] = plane_friction
-        v['gender'][0] = 0 if gender == 'male' else 1
+        write_env_tail(v, draw, env_seed, b.nfood)
         v['target'][0] = target
         v['food_alive'][0] = (1 << b.nfood) - 1
         v['food_active'][0] = (1 << b.nfood) - 1
-        v['iteration'][0] = 0
-        v['task_success'][0] = 0
-        v['total_food'][0] = b.nfood
-        v['rng'][0, 0] = (env_seed * 2654435761 + 12345) & 0x7FFFFFFF
-        v['rng'][0, 1] = (env_seed ^ 0x5bd1e995) & 0x7FFFFFFF
         if info is not None:
-            info.update(gender=gender, impairment=impairment, limit_scale=limit_scale, strength=strength, tremors=tremors,
+            info.update(gender=draw.gender, impairment=draw.impairment, limit_scale=draw.limit_scale, strength=draw.strength, tremors=draw.tremors,
                         ik_ok=ok, ik_restarts=restarts, ik_pos_err=best_d, target_ee_pos=target_ee_pos)
         return state_row
 
@@ -221,14 +181,7 @@ def make_states(blob, n, seed=1001, impairment='random', checker=None, **kw):
     rs = FeedingJacoReset(blob)
     st = blob.new_state(n)
     infos = [{} for _ in range(n)]
-
-    def draw(i, attempt=0):
-        rs.sample(np.random.RandomState(seed + i), st[i:i + 1], env_seed=seed + i, impairment=impairment, info=infos[i], attempt=attempt, **kw)
-    for i in range(n):
-        draw(i)
-    if checker is not None and (rs.toc is not None or blob.meta.get('mount') == 'mobile'):
-        from .reset_bed import reject_collisions
-        flags = reject_collisions(st, checker, draw)
-        for i in range(n):
-            infos[i]['collision_flags'] = int(flags[i])
+    placed = rs.toc is not None or rs.mobile is not None
+    sample_batch(n, seed, lambda i, rng, attempt: rs.sample(rng, st[i:i + 1], env_seed=seed + i, impairment=impairment, info=infos[i], attempt=attempt, **kw),
+                 checker if placed else None, infos, st)
     return st, infos

@@ -10,77 +10,46 @@ waist, elbow, stomach (:162), the scooper in the gripper (:154,173), gravity -9.
 
 Both settles need the stepper: `settler` is the rag-doll settle of host/reset_bed.py (RagdollSettler), `arm_settler` advances
 arm-manipulation state records by n stepSimulation calls at gravity -1 (ArmFallSettler: on the device, the robot and its tool parked
-out of reach); tests pass oracle-backed ones.  As in host/reset_bed.py: Bullet's IK is replaced by damped least squares and
-init_robot_pose's collision loop is not run.
+out of reach); tests pass oracle-backed ones.  The sampler holds a BasePoseSearch (host/base_pose.py: Bullet's IK is replaced by damped least
+squares) and a BedSurface (host/reset_bed.py) of its own; init_robot_pose's collision loop runs only with a `checker`.
 """
 import numpy as np
 
 from ..model import compiler as L
-from ..model import xform as X
-from .reset_bed import ArmChain, BedBathingSawyerReset, settle_record, settled_pose, placement_rng, reject_collisions
+from .base_pose import BasePoseSearch
+from .common import DeviceBatch, IDENTITY, draw_of, write_human_frames, open_gripper, tool_com_pose, write_env_tail, placement_rng, flag_collisions
+from .reset_bed import BedSurface, pose_in_air, rest_on_bed
 
 D = np.deg2rad
 PARKED = np.array([20.0, 20.0, 0.975])          # where the robot stands while the arm falls (it is not yet placed then, :162)
 
 
-class ArmManipulationSawyerReset(BedBathingSawyerReset):
+class ArmManipulationSawyerReset:
     def __init__(self, blob):
         assert blob.task_kind == L.TASK_ARM_MANIPULATION
         self.blob = blob
-        self.arm = ArmChain(blob)
         self.dual = bool(blob.meta.get('dual'))          # a two-armed robot: tool_right in the right hand (self.arm), tool_left in the left (self.arm2)
-        self.arm2 = ArmChain(blob, second=True) if self.dual else None
-        self.human_bodies = blob.meta['human_bodies']
-        self.human_dyn = blob.meta['human_dynamic_joints']
-        m = blob.meta
-        self.toc_base = np.array([-0.85, -0.4, 0]) + np.array(m.get('toc_base', [-0.3, 0.6, 0.975]))     # robot.py:142 + toc_base_pos_offset (sawyer.py:40)
-        self.ee_R = X.quat_to_mat(X.quat_from_rpy(m.get('ee_rpy', [0, -np.pi / 2.0, np.pi])))            # toc_ee_orient_rpy (sawyer.py:46)
-        self.self_guard = m.get('robot', 'sawyer') == 'sawyer'                                            # see _arm_in_pedestal
-        self._hm = {}
+        # toc_base_pos_offset (sawyer.py:40), toc_ee_orient_rpy (sawyer.py:46)
+        self.search = BasePoseSearch(blob, toc_base=[-0.3, 0.6, 0.975], ee_rpy=[0, -np.pi / 2.0, np.pi], self_guard=blob.meta.get('robot', 'sawyer') == 'sawyer', dual=self.dual)
+        self.arm, self.arm2 = self.search.arm, self.search.arm2
+        self.bed = BedSurface(blob)
 
     def pre_settle(self, rng, impairment='no_tremor', gender='random', human_q_override=None):
-        pre = BedBathingSawyerReset.pre_settle(self, rng, impairment, gender, human_q_override)
-        pre['base_pos'] = np.array([-0.25, 0.2, 0.95])                                       # arm_manipulation.py:123
-        return pre
-
-    def _fill_human(self, v, pre):
-        hm, hq, base_pos, base_quat = pre['hm'], pre['hq'], pre['base_pos'], pre['base_quat']
-        hpos, hquat = hm.fk(base_pos, base_quat, hq)
-        for k, link in enumerate(self.human_bodies):
-            if link < 0:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = base_pos, base_quat
-            else:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = hpos[link], hquat[link]
-        return hpos
+        return pose_in_air(rng, self.blob, impairment, gender, human_q_override, [-0.25, 0.2, 0.95])      # arm_manipulation.py:123
 
     def _place(self, v, rb_pos, rb_quat, q_arm, q_arm2=None):
         """robot joints, base and the tool(s) in the gripper(s) (tool.py:49-62)"""
         b, nr = self.blob, self.blob.nrobot
-        q = np.zeros(nr)
-        for k, d in enumerate(self.arm.chain):
-            q[d] = q_arm[k]
-        if self.dual:
-            for k, d in enumerate(self.arm2.chain):
-                q[d] = q_arm2[k]
-        for d in range(nr):                                                        # gripper open position, set instantly (:170)
-            if b.robot_i(d, 'ACT') < 0:
-                q[d] = min(max(b.robot_f(d, 'QT0'), b.robot_f(d, 'LOWER')), b.robot_f(d, 'UPPER'))
+        q = open_gripper(b, self.search.arm_joints(q_arm, q_arm2))                 # :170
         v['q'][0, :nr] = q
         v['qd'][0, :nr] = 0
         v['qt'][0, :nr] = q
         v['base'][0, :3], v['base'][0, 3:] = rb_pos, rb_quat
-        pe, Re, _, _ = self.arm.fk(np.asarray(rb_pos)[None], X.quat_to_mat(rb_quat)[None], q_arm[None])
-        tp, tq = X.compose(pe[0], X.mat_to_quat(Re[0]), b.task_f('TOOL_POS', 3), b.task_f('TOOL_QUAT', 4))
-        ip, iq = X.invert(b.free_f(0, 'REFPOS', 3), b.free_f(0, 'REFQUAT', 4))
-        cp, cq = X.compose(tp, tq, ip, iq)
         free = v['free'][0]
         free[:] = 0
-        free[0, :3], free[0, 3:7] = cp, cq
+        free[0, :3], free[0, 3:7] = tool_com_pose(b, 0, *self.search.tool_pose(rb_pos, rb_quat, q_arm))
         if self.dual:
-            pe, Re, _, _ = self.arm2.fk(np.asarray(rb_pos)[None], X.quat_to_mat(rb_quat)[None], q_arm2[None])
-            tp, tq = X.compose(pe[0], X.mat_to_quat(Re[0]), b.task_f('TOOL2_POS', 3), b.task_f('TOOL2_QUAT', 4))
-            ip, iq = X.invert(b.free_f(1, 'REFPOS', 3), b.free_f(1, 'REFQUAT', 4))
-            free[1, :3], free[1, 3:7] = X.compose(tp, tq, ip, iq)
+            free[1, :3], free[1, 3:7] = tool_com_pose(b, 1, *self.search.tool_pose(rb_pos, rb_quat, q_arm2, second=True))
 
     def arm_fall_record(self, state_row, pre, env_seed=0):
         """the record the second settle starts from (:136-142): the human resting, its right arm posed, the robot parked"""
@@ -93,14 +62,10 @@ class ArmManipulationSawyerReset(BedBathingSawyerReset):
         hq[3], hq[4], hq[6] = D(60), D(-60), 0.0                                   # j_right_shoulder_x / _y, j_right_elbow (:139)
         hq = hm.clamp(hq)                                                          # enforce_joint_limits (human.py:121)
         pre['hq'] = hq
-        self._fill_human(v, pre)
-        lo, hi = self.arm.lower, self.arm.upper                                     # parked at the middle of its joint ranges (the Jaco's zero pose violates its limits)
-        mid2 = None
-        if self.dual:
-            lo2, hi2 = self.arm2.lower, self.arm2.upper
-            mid2 = np.where((lo2 > -1e9) & (hi2 < 1e9), 0.5 * (lo2 + hi2), 0.0)
-        self._place(v, PARKED, np.array([0, 0, 0, 1.0]), np.where((lo > -1e9) & (hi < 1e9), 0.5 * (lo + hi), 0.0), mid2)
-        hq_dyn = np.array([hq[j] for j in self.human_dyn])
+        write_human_frames(v, b.meta['human_bodies'], *hm.fk(pre['base_pos'], pre['base_quat'], hq), pre['base_pos'], pre['base_quat'])
+        mid = [np.where((a.lower > -1e9) & (a.upper < 1e9), 0.5 * (a.lower + a.upper), 0.0) for a in (self.arm, self.arm2) if a is not None]
+        self._place(v, PARKED, IDENTITY, *mid)            # parked at the middle of its joint ranges (the Jaco's zero pose violates its limits)
+        hq_dyn = np.array([hq[j] for j in b.meta['human_dynamic_joints']])
         v['q'][0, nr:] = hq_dyn
         v['qt'][0, nr:] = hq_dyn
         v['qd'][0, nr:] = 0
@@ -111,11 +76,7 @@ class ArmManipulationSawyerReset(BedBathingSawyerReset):
         v['human_kp'][0] = 0.0 if b.is_coop else 0.05
         v['human_maxf'][0] = 0.0 if b.is_coop else 0.01 * pre['strength']
         v['limit_scale'][0] = pre['limit_scale']
-        v['plane_friction'][0] = pre['plane_friction']
-        v['gender'][0] = 0 if pre['gender'] == 'male' else 1
-        v['total_food'][0] = 1
-        v['rng'][0, 0] = (env_seed * 2654435761 + 12345) & 0x7FFFFFFF
-        v['rng'][0, 1] = (env_seed ^ 0x5bd1e995) & 0x7FFFFFFF
+        write_env_tail(v, draw_of(pre), env_seed, 1)
         return state_row
 
     def post_fall(self, rng, state_row, pre, env_seed=0, info=None, attempt=0):
@@ -124,7 +85,7 @@ class ArmManipulationSawyerReset(BedBathingSawyerReset):
         v = b.view(state_row)
         nr = b.nrobot
         hm, hq = pre['hm'], pre['hq'].copy()
-        for k, j in enumerate(self.human_dyn):
+        for k, j in enumerate(b.meta['human_dynamic_joints']):
             hq[j] = v['q'][0, nr + k]
         hpos, _ = hm.fk(pre['base_pos'], pre['base_quat'], hq)
         elbow, wrist, stomach, waist = hpos[7], hpos[9], hpos[24], hpos[27]        # :148-151
@@ -133,18 +94,11 @@ class ArmManipulationSawyerReset(BedBathingSawyerReset):
             pre['target_ee_left_pos'] = np.array([-1, 0.7, 0.8]) + rng.uniform(-0.05, 0.05, size=3)                    # :159 (drawn for a single arm as well)
         target_ee_pos = pre['target_ee_pos']
         prng = placement_rng(rng, env_seed, attempt)
-        toc, q_arm2 = None, None
-        for _ in range(4):
-            if self.dual:     # :165: the right arm's goals are wrist and waist, the left arm's elbow and stomach
-                toc = self._toc_dual(prng, [self.arm, self.arm2], [target_ee_pos, pre['target_ee_left_pos']], [[wrist, waist], [elbow, stomach]])
-            else:
-                toc = self._toc(prng, target_ee_pos, [wrist, waist, elbow, stomach])   # :162
-            if toc is not None:
-                break
-        assert toc is not None, 'no reachable base pose found'
-        rb_pos, rb_quat, q_arm, ngoal, manip = toc
-        if self.dual:
-            q_arm, q_arm2 = q_arm
+        if self.dual:     # :165: the right arm's goals are wrist and waist, the left arm's elbow and stomach
+            rb_pos, rb_quat, (q_arm, q_arm2), ngoal, manip = self.search.search_dual(prng, [target_ee_pos, pre['target_ee_left_pos']], [[wrist, waist], [elbow, stomach]])
+        else:
+            rb_pos, rb_quat, q_arm, ngoal, manip = self.search.search(prng, target_ee_pos, [wrist, waist, elbow, stomach])   # :162
+            q_arm2 = None
         self._place(v, rb_pos, rb_quat, q_arm, q_arm2)
         v['iteration'][0] = 0
         v['task_success'][0] = 0
@@ -155,26 +109,15 @@ class ArmManipulationSawyerReset(BedBathingSawyerReset):
         return state_row
 
 
-class ArmFallSettler:
+class ArmFallSettler(DeviceBatch):
     """Runs the second settle of ArmManipulationEnv.reset on the device: agx_settle on the arm-manipulation model with the human's gravity
-    set to the reset's -1 (arm_manipulation.py:125,145-146).  Fails loudly without a GPU."""
+    set to the reset's -1 (arm_manipulation.py:125,145-146)."""
 
     def __init__(self, blob, n_envs, device=0):
-        from ..libagx import Stepper
-        self.blob = blob.set_param('HUMAN_GRAVITY_Z', -1.0)
-        self.ctx = Stepper(self.blob, n_envs, device)
-        self.n = n_envs
+        DeviceBatch.__init__(self, blob.set_param('HUMAN_GRAVITY_Z', -1.0), n_envs, device)
 
     def __call__(self, states, n_sim_steps):
-        n = len(states)
-        assert n <= self.n
-        buf = self.blob.new_state(self.n)
-        buf[:n] = states
-        buf[n:] = states[:1]
-        self.ctx.set_state(buf)
-        self.ctx.settle(n_sim_steps)
-        self.ctx.L.agx_synchronize(self.ctx.h, None)
-        return self.ctx.get_state()[:n]
+        return self.settle(states, n_sim_steps)
 
 
 def make_states(blob, n, seed=1001, impairment='no_tremor', settler=None, arm_settler=None, fall_steps=100, checker=None, **kw):
@@ -188,28 +131,18 @@ def make_states(blob, n, seed=1001, impairment='no_tremor', settler=None, arm_se
     rngs = [np.random.RandomState(seed + i) for i in range(n)]
     pres = [rs.pre_settle(rngs[i], impairment=impairment, **kw) for i in range(n)]
     if settler is None:
-        r = blob.meta['ranges']
-        rs._bed = [blob.collider(c)['verts'] for c in range(*r['bed'])]
-        rs._bed_box = np.array([[v.min(0), v.max(0)] for v in rs._bed])
         for p in pres:
-            p['base_pos'] = rs._drop(p['hm'], p['base_pos'], p['base_quat'], p['hq'])
+            p['base_pos'] = rs.bed.drop(p['hm'], p['base_pos'], p['base_quat'], p['hq'])
     else:
-        from ..blob import ModelBlob
-        sblob = settler.blob if hasattr(settler, 'blob') else ModelBlob.load('bed_settle')
-        ss = sblob.new_state(n)
-        for i, p in enumerate(pres):
-            settle_record(sblob, ss[i:i + 1], p['gender'], p['limit_scale'], p['base_pos'], p['base_rpy'], p['hq'], p['plane_friction'])
-        ss = settler(ss)
-        for i, p in enumerate(pres):
-            p['base_pos'], p['base_quat'], p['hq'] = settled_pose(sblob, ss[i:i + 1], p['hm'])
+        rest_on_bed(settler, pres)
     for i, p in enumerate(pres):
         rs.arm_fall_record(st[i:i + 1], p, env_seed=seed + i)
     if arm_settler is not None:
         st = np.ascontiguousarray(arm_settler(st, fall_steps))
-    for i, p in enumerate(pres):
-        rs.post_fall(rngs[i], st[i:i + 1], p, env_seed=seed + i, info=infos[i])
-    if checker is not None:
-        flags = reject_collisions(st, checker, lambda i, attempt: rs.post_fall(rngs[i], st[i:i + 1], pres[i], env_seed=seed + i, info=infos[i], attempt=attempt))
-        for i in range(n):
-            infos[i]['collision_flags'] = int(flags[i])
+
+    def place(i, attempt=0):
+        rs.post_fall(rngs[i], st[i:i + 1], pres[i], env_seed=seed + i, info=infos[i], attempt=attempt)
+    for i in range(n):
+        place(i)
+    flag_collisions(st, checker, place, infos)
     return st, infos

@@ -9,15 +9,16 @@ Robot.position_robot_toc (env.py:276-310, robot.py:123-215) for the base and arm
 (env.py:295-297, robot.py:84-121) from the fixed base of a wheelchair-mounted one (scratch_itch.py:97-99), the gripper (:120), generate_target
 (:134-146: limb draw + Util.point_on_capsule, util.py:58-78).
 
-As in host/reset_bed.py (whose TOC search and batched IK this reuses): Bullet's IK is replaced by damped least squares and the
-collision rejection loop of init_robot_pose is not run.
+The placement is host/base_pose.py's (BasePoseSearch: Bullet's IK is replaced by damped least squares); the collision rejection loop of
+init_robot_pose runs only with a `checker`.
 """
 import numpy as np
 
 from ..model import compiler as L
 from ..model import xform as X
-from ..model.human import HumanModel
-from .reset_bed import ArmChain, BedBathingSawyerReset, mat_to_quat_batch, placement_rng, reject_collisions
+from .base_pose import BasePoseSearch
+from .common import (IDENTITY, draw_human, human_model, seated_base, write_human_frames, open_gripper, write_joints, write_reactive_hold, tool_com_pose,
+                     write_env_tail, placement_rng, sample_batch)
 
 D = np.deg2rad
 
@@ -31,106 +32,78 @@ def point_on_limb(rng, radius, length):
     return rl * axis + radius * np.cos(th) * ortho + radius * np.sin(th) * normal
 
 
-class ScratchItchReset(BedBathingSawyerReset):
-    def __init__(self, blob):
-        assert blob.task_kind == L.TASK_SCRATCH_ITCH
-        self.blob = blob
+def seated_placement(rs, prng, target_ee_pos, goals, wheelchair_yaw, human, **toc_kw):
+    """init_robot_pose (env.py:276-310) of a task with a seated human (scratch itch, dressing), by the sampler's mount: a robot on wheels is
+    drawn in place, a wheelchair-mounted arm solves IK restarts from its fixed base clear of the human, a free-standing robot searches its base
+    pose -> (base position, base quaternion, joint vector, arm angles or None, goals reached, manipulability)"""
+    if rs.mount == 'mobile':
+        return rs.mobile.draw(prng) + (None, 0, 0.0)
+    if rs.mount == 'wheelchair':
+        res = rs.search._mounted_ik(prng, target_ee_pos, rs.fixed_base, X.quat_from_rpy([0, 0, wheelchair_yaw]), human=human)
+    else:
+        res = rs.search.search(prng, target_ee_pos, goals, **toc_kw)
+    return res[:2] + (rs.search.arm_joints(res[2]),) + res[2:]
+
+
+class SeatedReset:
+    """what the samplers of the two tasks with a seated human and an arm to reach (scratch itch, dressing) are built from: the mount and its placement"""
+
+    def __init__(self, blob, toc_base, ee_rpy):
         m = blob.meta
-        self.mount = m.get('mount', 'toc')
+        self.blob, self.mount = blob, m.get('mount', 'toc')
+        self.arm, self.mobile, self.search = None, None, None
         if self.mount == 'mobile':                                  # the Stretch: no arm chain to solve (env.py:282-293)
             from .reset import MobilePlacement
-            self.arm, self.mobile = None, MobilePlacement(blob)
+            self.mobile = MobilePlacement(blob)
         else:
-            self.arm = ArmChain(blob)
-        self.human_bodies = blob.meta['human_bodies']
-        self.human_dyn = blob.meta['human_dynamic_joints']
-        self.toc_base = np.array([-0.85, -0.4, 0]) + np.array(m.get('toc_base', [0.1, 0, 0]))       # robot.py:142 + toc_base_pos_offset (pr2.py:35)
-        self.fixed_base = np.array([0, 0, 0.06]) + np.array(m.get('toc_base', [0, 0, 0]))          # wheelchair position + offset (scratch_itch.py:97-99)
-        self.ee_R = X.quat_to_mat(X.quat_from_rpy(m.get('ee_rpy', [0, 0, 0])))                      # toc_ee_orient_rpy (pr2.py:41)
-        self.self_guard = m.get('robot') == 'sawyer'                                                 # see reset_bed._arm_in_pedestal
-        self._hm = {}
+            self.search = BasePoseSearch(blob, toc_base=toc_base, ee_rpy=ee_rpy, self_guard=m.get('robot') == 'sawyer')
+            self.arm = self.search.arm
+        self.fixed_base = np.array([0, 0, 0.06]) + np.array(m.get('toc_base', [0, 0, 0]))          # wheelchair position + offset (scratch_itch.py:97-99, dressing.py:116-118)
+
+    def seated_human(self, rng, v, impairment, gender, preset, human_q_override, cloth=False):
+        """the draws of build_assistive_env, the seated human with the task's joint preset (degrees), its frames in the record
+        -> (draw, model, joint angles, link positions, link quaternions, base)"""
+        draw = draw_human(rng, impairment, gender, self.blob.nhdof, 10)            # human.py:91-92
+        hm = human_model(draw.gender, draw.limit_scale, cloth=cloth)
+        hq = hm.clamp(np.zeros(hm.n))                                              # human_creation.py:301-314
+        for j, a in preset:
+            hq[j] = D(a)
+        for j, a in (human_q_override or {}).items():                              # tests only
+            hq[j] = a
+        hq = hm.clamp(hq)
+        hbase = seated_base(draw.gender)
+        hpos, hquat = hm.fk(hbase, IDENTITY, hq)
+        write_human_frames(v, self.blob.meta['human_bodies'], hpos, hquat, hbase, [0, 0, 0, 1])
+        return draw, hm, hq, hpos, hquat, hbase
+
+    def write_robot_and_arm(self, v, draw, hq, q, rb_pos, rb_quat, reactive_gain):
+        """gripper, joints; the human's arm stays dynamic: controllable, or held by the reactive PD (reactive_force = 1, human.py:108,124-127)"""
+        b = self.blob
+        open_gripper(b, q)
+        write_joints(v, b, q, np.array([hq[j] for j in b.meta['human_dynamic_joints']]), draw, 0, rb_pos, rb_quat)
+        write_reactive_hold(v, b, draw, reactive_gain, 1.0)
+
+
+class ScratchItchReset(SeatedReset):
+    def __init__(self, blob):
+        assert blob.task_kind == L.TASK_SCRATCH_ITCH
+        SeatedReset.__init__(self, blob, toc_base=[0.1, 0, 0], ee_rpy=[0, 0, 0])  # toc_base_pos_offset (pr2.py:35), toc_ee_orient_rpy (pr2.py:41)
 
     def sample(self, rng, state_row, env_seed=0, impairment='random', gender='random', info=None, human_q_override=None, attempt=0):
         """attempt > 0: a re-draw of the robot's placement only (init_robot_pose's rejection loop), everything else as on attempt 0"""
         b = self.blob
         v = b.view(state_row)
-        nr, nh = b.nrobot, b.nhdof
-        plane_friction = rng.uniform(0.025, 0.5)                                   # env.py:120
-        if gender not in ('male', 'female'):
-            gender = rng.choice(['male', 'female'])                                # human.py:76-77
-        if impairment == 'random':
-            impairment = rng.choice(['none', 'limits', 'weakness', 'tremor'])      # human.py:80-81
-        elif impairment == 'no_tremor':
-            impairment = rng.choice(['none', 'limits', 'weakness'])
-        limit_scale = 1.0 if impairment != 'limits' else rng.uniform(0.5, 1.0)     # human.py:85
-        strength = 1.0 if impairment != 'weakness' else rng.uniform(0.25, 1.0)     # human.py:86
-        tremors = np.zeros(nh)
-        if impairment == 'tremor':
-            tremors = rng.uniform(D(-10), D(10), size=nh)                          # human.py:91-92
-        rng.uniform(0.4, 0.8)                                                      # skin colour, human_creation.py:63
-        hm = self._human(gender, limit_scale)
-        hq = hm.clamp(np.zeros(hm.n))                                              # human_creation.py:301-314
-        for j, a in [(3, 30), (6, -90), (16, -90), (28, -90), (31, 80), (35, -90), (38, 80)]:     # scratch_itch.py:104
-            hq[j] = D(a)
-        for j, a in (human_q_override or {}).items():                              # tests only
-            hq[j] = a
-        hq = hm.clamp(hq)
-        hbase = np.array([0, 0.03, 0.89 if gender == 'male' else 0.86])            # human.py:102
-        hpos, hquat = hm.fk(hbase, np.array([0, 0, 0, 1.0]), hq)
-        for k, link in enumerate(self.human_bodies):
-            if link < 0:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = hbase, [0, 0, 0, 1]
-            else:
-                v['human'][0, k, :3], v['human'][0, k, 3:] = hpos[link], hquat[link]
+        preset = [(3, 30), (6, -90), (16, -90), (28, -90), (31, 80), (35, -90), (38, 80)]     # scratch_itch.py:104
+        draw, hm, hq, hpos, hquat, hbase = self.seated_human(rng, v, impairment, gender, preset, human_q_override)
         shoulder, elbow, wrist = hpos[5], hpos[7], hpos[9]                         # scratch_itch.py:107-109
         target_ee_pos = np.array([-0.6, 0, 0.8]) + rng.uniform(-0.05, 0.05, size=3)    # scratch_itch.py:115
-        toc = None
         prng = placement_rng(np.random.RandomState(rng.randint(1 << 31)), env_seed, attempt)     # one draw of the main stream, whatever the attempt
-        if self.mount == 'mobile':
-            toc = self.mobile.draw(prng) + (0, 0.0)
-        elif self.mount == 'wheelchair':
-            toc = self._mounted_ik(prng, target_ee_pos, self.fixed_base, X.quat_from_rpy([0, 0, -np.pi / 2.0]), human=(hm, hpos, hquat, hbase))   # scratch_itch.py:99
-        else:
-            for _ in range(4):
-                toc = self._toc(prng, target_ee_pos, [shoulder, elbow, wrist])
-                if toc is not None:
-                    break
-        assert toc is not None, 'no reachable base pose found'
-        rb_pos, rb_quat, q_arm, ngoal, manip = toc
-        if self.mount == 'mobile':
-            q = q_arm.copy()
-        else:
-            q = np.zeros(nr)
-            for k, d in enumerate(self.arm.chain):
-                q[d] = q_arm[k]
-        for d in range(nr):                                                        # gripper open position, set instantly (scratch_itch.py:120)
-            if b.robot_i(d, 'ACT') < 0:
-                q[d] = min(max(b.robot_f(d, 'QT0'), b.robot_f(d, 'LOWER')), b.robot_f(d, 'UPPER'))
-        v['q'][0, :nr] = q
-        v['qd'][0] = 0
-        v['qt'][0, :nr] = q
-        hq_dyn = np.array([hq[j] for j in self.human_dyn])
-        v['q'][0, nr:] = hq_dyn
-        v['qt'][0, nr:] = hq_dyn
-        v['tremor'][0] = tremors
-        v['tremor_target'][0] = hq_dyn                                             # human.py:123 target_joint_angles
-        # the controllable joints stay dynamic: controllable, or held by the reactive PD (reactive_force = 1, human.py:108,124-127)
-        v['frozen'][0] = 0
-        agent = b.is_coop or impairment == 'tremor'                                # then take_step re-sets the motors every step (env.py:130-131,222)
-        v['human_kp'][0] = 0.0 if agent else 0.01                                  # reactive_gain, scratch_itch.py:105
-        v['human_maxf'][0] = 0.0 if agent else 1.0 * strength
-        v['limit_scale'][0] = limit_scale
-        v['base'][0, :3], v['base'][0, 3:] = rb_pos, rb_quat
-        if self.mount == 'mobile':
-            tp, tq = self.mobile.kin.tool_pose(rb_pos, rb_quat, q)
-        else:
-            pe, Re, _, _ = self.arm.fk(rb_pos[None], X.quat_to_mat(rb_quat)[None], q_arm[None])
-            tp, tq = X.compose(pe[0], X.mat_to_quat(Re[0]), b.task_f('TOOL_POS', 3), b.task_f('TOOL_QUAT', 4))      # tool.py:49-62
-        ip, iq = X.invert(b.free_f(0, 'REFPOS', 3), b.free_f(0, 'REFQUAT', 4))
-        cp, cq = X.compose(tp, tq, ip, iq)
+        rb_pos, rb_quat, q, q_arm, ngoal, manip = seated_placement(self, prng, target_ee_pos, [shoulder, elbow, wrist], -np.pi / 2.0, (hm, hpos, hquat, hbase))   # scratch_itch.py:99
+        self.write_robot_and_arm(v, draw, hq, q, rb_pos, rb_quat, 0.01)            # gripper: scratch_itch.py:120; reactive_gain: :105
+        tp, tq = self.mobile.kin.tool_pose(rb_pos, rb_quat, q) if q_arm is None else self.search.tool_pose(rb_pos, rb_quat, q_arm)      # tool.py:49-62
         free = v['free'][0]
         free[:] = 0
-        free[0, :3], free[0, 3:7] = cp, cq
+        free[0, :3], free[0, 3:7] = tool_com_pose(b, 0, tp, tq)
         # generate_target (scratch_itch.py:134-146): limb, then a point on its capsule (util.py:58-78)
         limb = int(rng.randint(2))
         radius, length = hm.dims['upperarm' if limb == 0 else 'forearm']
@@ -139,15 +112,9 @@ class ScratchItchReset(BedBathingSawyerReset):
         task[:] = 0
         task[L.SI['TARGET']:L.SI['TARGET'] + 3] = target_on_arm.astype(np.float32).view(np.int32)
         task[L.SI['LIMB']] = limb
-        v['plane_friction'][0] = plane_friction
-        v['gender'][0] = 0 if gender == 'male' else 1
-        v['iteration'][0] = 0
-        v['task_success'][0] = 0
-        v['total_food'][0] = 1                                                      # task_success >= 1 x task_success_threshold (scratch_itch.py:37)
-        v['rng'][0, 0] = (env_seed * 2654435761 + 12345) & 0x7FFFFFFF
-        v['rng'][0, 1] = (env_seed ^ 0x5bd1e995) & 0x7FFFFFFF
+        write_env_tail(v, draw, env_seed, 1)                                        # task_success >= 1 x task_success_threshold (scratch_itch.py:37)
         if info is not None:
-            info.update(gender=gender, impairment=impairment, limit_scale=limit_scale, strength=strength, tremors=tremors, limb=limb,
+            info.update(gender=draw.gender, impairment=draw.impairment, limit_scale=draw.limit_scale, strength=draw.strength, tremors=draw.tremors, limb=limb,
                         toc_goals=ngoal, toc_manipulability=manip, target_ee_pos=target_ee_pos, human_q=hq, target_on_arm=target_on_arm)
         return state_row
 
@@ -158,15 +125,8 @@ def make_states(blob, n, seed=1001, impairment='random', checker=None, **kw):
     rs = ScratchItchReset(blob)
     st = blob.new_state(n)
     infos = [{} for _ in range(n)]
-
-    def draw(i, attempt=0):
-        rs.sample(np.random.RandomState(seed + i), st[i:i + 1], env_seed=seed + i, impairment=impairment, info=infos[i], attempt=attempt, **kw)
-    for i in range(n):
-        draw(i)
-    if checker is not None:
-        flags = reject_collisions(st, checker, draw)
-        for i in range(n):
-            infos[i]['collision_flags'] = int(flags[i])
+    sample_batch(n, seed, lambda i, rng, attempt: rs.sample(rng, st[i:i + 1], env_seed=seed + i, impairment=impairment, info=infos[i], attempt=attempt, **kw),
+                 checker, infos, st)
     return st, infos
 
 

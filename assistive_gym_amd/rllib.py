@@ -302,7 +302,7 @@ class AgxPipelinedBatchEnv(_BaseEnv):
         for h in range(2):
             v = self.halves[h]
             if h == 1:
-                v.pool, v.pool_host = self.halves[0].pool, self.halves[0].pool_host          # one pool for both halves (drawn by GLOBAL env index)
+                v.share_pool(self.halves[0])          # one pool for both halves (drawn by GLOBAL env index), garments included
             with torch.cuda.stream(self.streams[h]):
                 first = v.reset(env_offset=h * n2)
                 self.pack.append(torch.empty((n2, 2 * od + 4), dtype=torch.float32, device=v.device))

@@ -8,156 +8,67 @@ import numpy as np
 import torch
 
 from .blob import ModelBlob
-from .host.reset import make_states
 from .libagx import Stepper
+from .reset_recipes import HostSampler, attach_settle_models, impairment_of, recipe, sample_on_device
+from .reset_recipes import RAGDOLL_SETTLE_STEPS, attach_arm_fall_models, attach_ragdoll_model      # noqa: F401 (tests import them from here)
 from .shard import episode_seed, pool_indices
 
-SETTLE_STEPS = 25   # feeding.py:178-179
-DRESSING_SETTLE_STEPS = 50   # dressing.py:186-187
-RAGDOLL_SETTLE_STEPS = 100   # bed_bathing.py:130-131
-DRINKING_SETTLE_STEPS = 50   # drinking.py:176-177: the water drops into the cup
+
+def _read_back(st, aux=()):
+    """-> (states, garments / water or None) of a stepper whose reset has been enqueued; closes it and the models attached to it"""
+    st.synchronize()
+    out = st.get_state(), st.get_cloth() if recipe(st.blob).extra else None
+    for h in (st,) + tuple(aux):
+        h.close()
+    return out
 
 
-def attach_ragdoll_model(stepper, n_envs, device):
-    """bed bathing: the stepper's reset generator reads the human's resting pose from the settled records of a second model, the rag doll
-    (bed_bathing.py:119-137): a Stepper on `bed_settle` with as many environments, attached through agx_attach_settle_model"""
-    rag = Stepper(ModelBlob.load('bed_settle'), n_envs, device)
-    stepper.attach_settle_model(rag, RAGDOLL_SETTLE_STEPS)
-    return rag
+def _device_pool(blob, n, seed, device, impairment):
+    st = Stepper(blob, n, device)
+    aux = attach_settle_models(st, blob, n, device)
+    sample_on_device(st, blob, seed, impairment, recipe(blob).fused)
+    return _read_back(st, aux)
 
 
-ARM_FALL_STEPS = 100         # arm_manipulation.py:145-146
-ARM_DROP_BASE = (-0.25, 0.2, 0.95)   # arm_manipulation.py:123
-
-
-def attach_arm_fall_models(stepper, blob, n_envs, device):
-    """arm manipulation: ArmManipulationEnv.reset has TWO settles (arm_manipulation.py:117-146) -- the rag doll (bed_settle,
-    dropped from its own spot) and the fall of the posed right arm, which runs on the task's own model at the reset's gravity of -1
-    (ModelBlob.fall_model()).  The fall handle is attached to the task's, the rag doll to the fall handle.  -> (fall, ragdoll) steppers"""
-    rag = Stepper(ModelBlob.load('bed_settle').with_drop_base(ARM_DROP_BASE), n_envs, device)
-    fall = Stepper(blob.fall_model(), n_envs, device)
-    fall.attach_settle_model(rag, RAGDOLL_SETTLE_STEPS)
-    stepper.attach_settle_model(fall, ARM_FALL_STEPS)
-    return fall, rag
+def _host_pool(blob, n, seed, device, impairment):
+    host = HostSampler(blob, n, device)
+    states, extra = host(n, seed, impairment)
+    if not host.row.host_settle:
+        return states, extra
+    st = Stepper(blob, n, device)
+    host.inject(st, states, extra)
+    return _read_back(st)
 
 
 def build_reset_pool(blob, pool_size, seed, device=0, impairment='random', sampler='device', _depth=0):
-    """pool_size post-reset states: FeedingEnv.reset's sampling (sampler 'device': agx_sample_reset on the GPU;
-    'host': the numpy path of host/reset.py), then the 25 settle steps of feeding.py:178-179 on the device.
-    BedBathingSawyer: BedBathingEnv.reset restated on the host (host/reset_bed.py) around the rag-doll settle on the device.
-    Returns a float32 (pool_size, state_words) array."""
+    """pool_size post-reset states, by the task's recipe (reset_recipes.py).  sampler 'device': the whole of <Task>Env.reset on the GPU -- the
+    settles of the attached models (rag doll, the arm's fall), the device-side reset generator, the task's own settle; 'host': the numpy
+    sampler under host/ around the same settles on the device.  Returns a float32 (pool_size, state_words) array, or (states, garments / water)
+    for the tasks whose pool entries carry one."""
     from .model import compiler as L
-    if blob.task_kind == L.TASK_BED_BATHING and blob.has_reset_generator and sampler == 'device':
-        # BedBathingEnv.reset on the device: the rag doll's drop record, its 100-step settle, then the sampler of this model (base pose search,
-        # tool, targets) reading the resting pose -- agx_sample_reset with the rag-doll model attached
-        st = Stepper(blob, pool_size, device)
-        rag = attach_ragdoll_model(st, pool_size, device)
-        st.sample_reset(seed, impairment=impairment)
-        st.synchronize()
-        out = st.get_state()
-        st.close(); rag.close()
-        return out
-    if blob.task_kind == L.TASK_BED_BATHING:
-        from .host.reset_bed import make_states as make_bed_states, RagdollSettler
-        # the rag-doll settle of BedBathingEnv.reset runs on the device (bed_settle kernel variant), the rest on the host
-        from .host.reset_bed import DeviceCollisionChecker
-        return make_bed_states(blob, pool_size, seed=seed, impairment=impairment, settler=RagdollSettler(pool_size, device),
-                               checker=DeviceCollisionChecker(blob, pool_size, device))[0]
-    if blob.task_kind == L.TASK_ARM_MANIPULATION and blob.has_reset_generator and sampler == 'device':
-        # ArmManipulationEnv.reset on the device: rag doll, the arm's fall in the fall model, then this model's sampler (one base pose for both arms of PR2 / Baxter)
-        st = Stepper(blob, pool_size, device)
-        fall, rag = attach_arm_fall_models(st, blob, pool_size, device)
-        st.sample_reset(seed, impairment='no_tremor' if impairment == 'random' else impairment)
-        st.synchronize()
-        out = st.get_state()
-        st.close(); fall.close(); rag.close()
-        return out
-    if blob.task_kind == L.TASK_ARM_MANIPULATION:
-        # ArmManipulationEnv.reset (host/reset_arm.py) around its two settles on the device: the rag doll, then the fall of the right arm
-        from .host.reset_arm import make_states as make_arm_states, ArmFallSettler
-        from .host.reset_bed import RagdollSettler, DeviceCollisionChecker
-        return make_arm_states(blob, pool_size, seed=seed, impairment='no_tremor' if impairment == 'random' else impairment,
-                               settler=RagdollSettler(pool_size, device), arm_settler=ArmFallSettler(blob, pool_size, device),
-                               checker=DeviceCollisionChecker(blob, pool_size, device))[0]
-    if blob.task_kind == L.TASK_SCRATCH_ITCH and blob.has_reset_generator and sampler == 'device':
-        # a wheelchair-mounted arm (Jaco, Panda) or a free-standing PR2 / Baxter (base pose search on the device): ScratchItchEnv.reset sampled by
-        # the device-side reset generator, as for the feeding scenes
-        st = Stepper(blob, pool_size, device)
-        st.sample_reset(seed, impairment=impairment)
-        st.synchronize()
-        out = st.get_state()
-        st.close()
-        return out
-    if blob.task_kind == L.TASK_SCRATCH_ITCH:
-        from .host.reset_scratch import make_states as make_scratch_states
-        from .host.reset_bed import DeviceCollisionChecker
-        return make_scratch_states(blob, pool_size, seed=seed, impairment=impairment, checker=DeviceCollisionChecker(blob, pool_size, device))[0]
-    if blob.task_kind == L.TASK_DRESSING and blob.has_reset_generator and sampler == 'device':
-        # DressingEnv.reset on the device: sampling (base pose search for Baxter / PR2), the garment at the end effector, the 50-step settle
-        # under half gravity, full gravity afterwards -- all inside agx_reset
-        st = Stepper(blob, pool_size, device)
-        st.reset(None, None, seed, impairment=impairment, settle_substeps=DRESSING_SETTLE_STEPS)
-        st.synchronize()
-        out = st.get_state(), st.get_cloth()
-        st.close()
-        return out
-    if blob.task_kind == L.TASK_DRINKING and sampler == 'device':
-        # DrinkingEnv.reset on the device (drinking.py:122-181): sampling (IK restarts / base pose search / placement draws), the water grid above
-        # the cup, the 50 steps in which it drops into the cup -- all inside agx_reset; returns (states, water): the particles of a pool
-        # entry travel with its state record like a garment
-        assert blob.has_reset_generator
-        st = Stepper(blob, pool_size, device)
-        st.reset(None, None, seed, impairment=impairment, settle_substeps=DRINKING_SETTLE_STEPS)
-        st.synchronize()
-        out = st.get_state(), st.get_cloth()
-        st.close()
-        return out
-    if blob.task_kind == L.TASK_DRINKING:
-        # the numpy sampler (host/reset_drinking.py: the wheelchair-mounted arms) around the device's 50-step settle
-        from .host.reset_drinking import make_states as make_drinking_states
-        states, water, _ = make_drinking_states(blob, pool_size, seed=seed, impairment=impairment)
-        st = Stepper(blob, pool_size, device)
-        st.set_state(states); st.set_cloth(water)
-        st.settle(DRINKING_SETTLE_STEPS)
-        st.synchronize()
-        out = st.get_state(), st.get_cloth()
-        st.close()
-        return out
-    if blob.task_kind == L.TASK_DRESSING:
-        # DressingEnv.reset restated on the host (host/reset_dressing.py) around the 50-step cloth settle on the device;
-        # returns (states, garments): the garment of a pool entry travels with its state record
-        from .host.reset_dressing import make_states as make_dressing_states, ClothSettler
-        from .host.reset_bed import DeviceCollisionChecker
-        st, cloth, _ = make_dressing_states(blob, pool_size, seed=seed, impairment=impairment, settler=ClothSettler(blob, pool_size, device),
-                                            checker=DeviceCollisionChecker(blob, pool_size, device))
-        return st, cloth
-    st = Stepper(blob, pool_size, device)
-    if blob.meta.get('mount') in ('toc', 'mobile') and not blob.has_reset_generator:      # a mobile robot (Stretch): placed by the numpy sampler (older blobs: base pose search on the host)
-        sampler = 'host'
-    if sampler == 'device':
-        st.sample_reset(seed, impairment=impairment)
-    elif sampler == 'host':
-        checker = None
-        if blob.meta.get('mount') in ('toc', 'mobile'):
-            from .host.reset_bed import DeviceCollisionChecker
-            checker = DeviceCollisionChecker(blob, pool_size, device)
-        states, _ = make_states(blob, pool_size, seed=seed, impairment=impairment, checker=checker)
-        st.set_state(states)
-    else:
+    if sampler not in ('device', 'host'):
         raise ValueError("sampler must be 'device' or 'host'")
-    st.settle(SETTLE_STEPS)
-    st.synchronize()
-    out = st.get_state()
-    st.close()
+    row = recipe(blob)
+    if sampler == 'device' and not blob.has_reset_generator:
+        # a blob without a reset section: the numpy sampler places its robot (a mounted feeding arm is still sampled on the device: it needs no placement)
+        assert blob.task_kind != L.TASK_DRINKING
+        if blob.task_kind != L.TASK_FEEDING or blob.meta.get('mount') in ('toc', 'mobile'):
+            sampler = 'host'
+    out, extra = (_device_pool if sampler == 'device' else _host_pool)(blob, pool_size, seed, device, impairment_of(blob, impairment))
     # A sampled start whose arm pose the IK restarts left deep inside the table or the bowl is pushed out by the contact rows with whatever
     # velocity closes the gap in one substep (no penetration-recovery clamp as in Bullet's split impulse): a few in a thousand blow up during
-    # the settle.  Such entries never enter a pool: they are drawn again from the seeds after this batch's.
-    bad = ~np.isfinite(out[:, :blob.h['S_ENV']]).all(axis=1)          # (the float part of a record: the env / task words hold integers)
+    # the settle.  Such entries never enter a pool: they are drawn again from the seeds after this batch's.  (The feeding row only.)
+    bad = ~np.isfinite(out[:, :blob.h['S_ENV']]).all(axis=1) if row.redraw else np.zeros(pool_size, dtype=bool)      # (the float part of a record: the env / task words hold integers)
     if bad.any() and _depth < 4:
         out[bad] = build_reset_pool(blob, int(bad.sum()), seed + pool_size, device, impairment, sampler, _depth + 1)
     elif bad.any():
         raise RuntimeError('%d of %d sampled reset states are not finite after the settle (seed %d)' % (bad.sum(), pool_size, seed))
-    return out
+    return (out, extra) if row.extra else out
+
+
+def _pair(pool):
+    """what build_reset_pool returned as (states, garments / water or None)"""
+    return pool if isinstance(pool, tuple) else (pool, None)
 
 
 def _refresh_worker(model, coop, seed, batch, device, impairment, sampler, queue):
@@ -239,9 +150,7 @@ class AssistiveVecEnv:
             self.blob = self.blob.coop()
         self.n_envs, self.device_index, self.seed = n_envs, device, seed
         self.device = torch.device('cuda', device)
-        from .model import compiler as _L
-        if self.blob.task_kind == _L.TASK_ARM_MANIPULATION and impairment == 'random':
-            impairment = 'no_tremor'                      # build_assistive_env(human_impairment='no_tremor'), arm_manipulation.py:112
+        impairment = impairment_of(self.blob, impairment)
         self.pool_size, self.impairment, self.auto_reset, self.reset_mode = pool_size, impairment, auto_reset, reset
         self.stepper = Stepper(self.blob, n_envs, device)
         self.act_dim, self.obs_dim = self.blob.act_dim, self.blob.obs_dim
@@ -249,7 +158,7 @@ class AssistiveVecEnv:
         self.reward = torch.zeros(n_envs, dtype=torch.float32, device=self.device)
         self.done = torch.zeros(n_envs, dtype=torch.uint8, device=self.device)
         self.info = torch.zeros((n_envs, 8), dtype=torch.float32, device=self.device)
-        self.pool = None
+        self.pool, self.pool_host, self.cloth_pool, self.cloth_pool_host = None, None, None, None
         self.episode_len = int(self.blob.task_f('EPISODE_LEN'))
         self.env_offset, self._t, self._episode = 0, 0, 0
         self.terminal_obs = None
@@ -261,14 +170,7 @@ class AssistiveVecEnv:
         self.start_states_redrawn = 0                 # reset='device': environments whose sampled start came out of the settle implausible and were drawn again
         # reset='device' of the models whose reset has settles of its own before the sampling: further handles attached to the stepper
         # (bed bathing: the rag doll; arm manipulation: the arm's fall, and the rag doll behind it) -- for whichever class or model name built this env
-        self._aux_steppers = ()
-        if self.reset_mode == 'device' and self.blob.has_reset_generator:
-            from .model import compiler as L
-            flags = int(self.blob.i[int(self.blob.i[L.H['OFF_RESET']]) + L.X_['FLAGS']])
-            if self.blob.task_kind == L.TASK_ARM_MANIPULATION and flags & 128:
-                self._aux_steppers = attach_arm_fall_models(self.stepper, self.blob, n_envs, self.device_index)
-            elif flags & 16:
-                self._aux_steppers = (attach_ragdoll_model(self.stepper, n_envs, self.device_index),)
+        self._aux_steppers = attach_settle_models(self.stepper, self.blob, n_envs, self.device_index) if self.reset_mode == 'device' else ()
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -277,9 +179,7 @@ class AssistiveVecEnv:
         """FeedingEnv.reset for the envs selected by mask (None = all), in place on the device: env i of episode e is
         sampled from episode_seed(seed, e, env_offset) + i -- a function of the GLOBAL env index and the episode only,
         i.e. independent of the number of GPUs the batch is spread over -- and settled for 25 substeps"""
-        from .model import compiler as L
-        # FeedingEnv.reset: 25 steps for the food to drop; DressingEnv.reset: 50 for the garment; ScratchItchEnv.reset has no settle loop
-        settle = {L.TASK_FEEDING: SETTLE_STEPS, L.TASK_DRESSING: DRESSING_SETTLE_STEPS, L.TASK_DRINKING: DRINKING_SETTLE_STEPS}.get(self.blob.task_kind, 0)
+        settle = recipe(self.blob).settle_steps
         self.stepper.reset(mask, None, episode_seed(self.seed, self._episode, self.env_offset), impairment=self.impairment,
                            settle_substeps=settle, stream=s)
         if settle > 0:
@@ -296,15 +196,36 @@ class AssistiveVecEnv:
                 self.start_states_redrawn += int(bad.sum())
         self._episode += 1
 
+    def _install_pool(self, states, cloth=None, idx=None):
+        """the pool is ONE thing: the states on the host and on the device and, for models with a cloth, a garment each, which the stepper's
+        pool draws (agx_reset_done) read as well.  idx None: a new pool; else those entries of the pool are overwritten in place (whoever
+        shares the pool sees them)"""
+        if idx is None:
+            self.pool_host = np.ascontiguousarray(states)
+            self.pool = torch.from_numpy(self.pool_host).to(self.device)
+            if cloth is not None:
+                self.cloth_pool_host = np.ascontiguousarray(cloth)
+                self.cloth_pool = torch.from_numpy(self.cloth_pool_host).to(self.device)
+                self.stepper.set_cloth_pool(self.cloth_pool)
+            return
+        on_dev = torch.from_numpy(idx).to(self.device)
+        self.pool_host[idx] = states
+        self.pool[on_dev] = torch.from_numpy(states).to(self.device)
+        if cloth is not None:
+            self.cloth_pool_host[idx] = cloth
+            self.cloth_pool[on_dev] = torch.from_numpy(cloth).to(self.device)
+
     def set_pool(self, states, cloth=None):
         """Use the given post-reset states (float32 [pool_size, state_words]; with a garment each for models with a cloth) as the reset
         pool instead of generating one -- e.g. a workload-specific pool (bench.py --workload wiping) or states sampled elsewhere."""
         assert states.dtype == np.float32 and states.shape == (self.pool_size, self.blob.state_words)
-        self.pool_host = np.ascontiguousarray(states)
-        self.pool = torch.from_numpy(self.pool_host).to(self.device)
-        if cloth is not None:
-            self.cloth_pool_host = np.ascontiguousarray(cloth)
-            self.cloth_pool = torch.from_numpy(self.cloth_pool_host).to(self.device)
+        self._install_pool(states, cloth)
+
+    def share_pool(self, other):
+        """Use `other`'s pool -- the same arrays on the host and on the device, garments included -- e.g. the two halves of one batch (rllib.py)"""
+        assert other.pool is not None and other.pool_size == self.pool_size
+        self.pool_host, self.pool, self.cloth_pool_host, self.cloth_pool = other.pool_host, other.pool, other.cloth_pool_host, other.cloth_pool
+        if self.cloth_pool is not None:
             self.stepper.set_cloth_pool(self.cloth_pool)
 
     def reset(self, env_offset=0):
@@ -322,19 +243,14 @@ class AssistiveVecEnv:
                 self.stepper.set_cloth_pool(self._rescue_cloth)
         else:
             if self.pool is None:
-                self.pool_host = build_reset_pool(self.blob, self.pool_size, self.seed, self.device_index, self.impairment,
-                                                  sampler='host' if self.reset_mode == 'host' else 'device')
-                if isinstance(self.pool_host, tuple):         # models with a cloth: (states, garments)
-                    self.pool_host, self.cloth_pool_host = self.pool_host
-                    self.cloth_pool = torch.from_numpy(self.cloth_pool_host).to(self.device)
-                    self.stepper.set_cloth_pool(self.cloth_pool)
-                self.pool = torch.from_numpy(self.pool_host).to(self.device)
+                self._install_pool(*_pair(build_reset_pool(self.blob, self.pool_size, self.seed, self.device_index, self.impairment,
+                                                           sampler='host' if self.reset_mode == 'host' else 'device')))
                 if self.pool_refresh > 0 and self._refresher is None:
                     self._refresher = PoolRefresher(self._model_name, self.blob.is_coop, self.seed, min(self.pool_refresh, self.pool_size), self.device_index, self.impairment,
                                                     'host' if self.reset_mode == 'host' else 'device', sync=self.pool_refresh_sync)
             idx = pool_indices(env_offset, self.n_envs, self.pool_size)
             self.stepper.set_state(self.pool_host[idx])
-            if getattr(self, 'cloth_pool_host', None) is not None:
+            if self.cloth_pool_host is not None:
                 self.stepper.set_cloth(self.cloth_pool_host[idx])
             self.stepper.set_env_offset(env_offset)       # later episodes draw from the pool by GLOBAL env index too
         self.stepper.observe_dev(self.obs, s)
@@ -382,14 +298,9 @@ class AssistiveVecEnv:
     def _swap_in_fresh_states(self):
         """batches the refresher has ready replace the oldest pool entries (round robin), states and -- for models with a cloth -- garments"""
         for b in self._refresher.poll():
-            states, cloth = b if isinstance(b, tuple) else (b, None)
+            states, cloth = _pair(b)
             k = len(states)
-            idx = (self._refresh_cursor + np.arange(k)) % self.pool_size
-            self.pool_host[idx] = states
-            self.pool[torch.from_numpy(idx).to(self.device)] = torch.from_numpy(states).to(self.device)
-            if cloth is not None:
-                self.cloth_pool_host[idx] = cloth
-                self.cloth_pool[torch.from_numpy(idx).to(self.device)] = torch.from_numpy(cloth).to(self.device)
+            self._install_pool(states, cloth, idx=(self._refresh_cursor + np.arange(k)) % self.pool_size)
             self._refresh_cursor = int((self._refresh_cursor + k) % self.pool_size)
             self.pool_refreshed += k
 

@@ -191,6 +191,7 @@ def test_vector_env_rows_are_never_overwritten_and_workers_slice_one_batch():
         h.close()
     # the asynchronous two-half BaseEnv: the same batch again, half by half
     p = AgxPipelinedBatchEnv('FeedingJaco-v1', n, pool_size=8)
+    assert p.halves[0].pool.data_ptr() == p.halves[1].pool.data_ptr()          # one pool for both halves
     for k in range(3):
         for h in range(2):
             obs, rew, done, info, _ = p.poll()
