@@ -1,7 +1,8 @@
 """Build libagx.so (HIP, gfx950) in-tree.  `python -m assistive_gym_amd.build`.
 
 The kernels are compiled once per variant (limits + task layer: one line of csrc/agx_variants.def, csrc/agx_kernels.hip) and linked with the handle /
-C-ABI code (csrc/agx_api.hip), the policy-step / GAE kernels (csrc/agx_policy.hip) and the end-effector IK kernels (csrc/agx_ik.hip)."""
+C-ABI code (csrc/agx_api.hip), the policy-step / GAE kernels (csrc/agx_policy.hip), the end-effector IK kernels (csrc/agx_ik.hip) and the camera's
+ray caster (csrc/agx_render.hip)."""
 import os
 import subprocess
 import sys
@@ -33,7 +34,8 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
     os.makedirs(objdir, exist_ok=True)
     jobs = [(os.path.join(objdir, 'agx_api.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_api.hip')]),
             (os.path.join(objdir, 'agx_policy.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_policy.hip')]),      # policy step + GAE (stateless entries)
-            (os.path.join(objdir, 'agx_ik.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_ik.hip')])]              # end-effector pose + IK (agx_ee_pose, agx_ee_ik)
+            (os.path.join(objdir, 'agx_ik.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_ik.hip')]),              # end-effector pose + IK (agx_ee_pose, agx_ee_ik)
+            (os.path.join(objdir, 'agx_render.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_render.hip')])]      # the camera's ray caster (agx_render)
     reuse = []
     for v in variants.VARIANTS:
         if only and v.name not in only:
@@ -44,6 +46,7 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
         jobs[0] = (os.path.join(HERE, 'lib', 'obj', 'agx_api.o'), None)
         jobs[1] = (os.path.join(HERE, 'lib', 'obj', 'agx_policy.o'), None)
         jobs[2] = (os.path.join(HERE, 'lib', 'obj', 'agx_ik.o'), None)
+        jobs[3] = (os.path.join(HERE, 'lib', 'obj', 'agx_render.o'), None)
     with ThreadPoolExecutor(len(jobs)) as ex:
         list(ex.map(lambda j: j[1] and subprocess.check_call(j[1] + ['-o', j[0]]), jobs))
     subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + [j[0] for j in jobs] + reuse)

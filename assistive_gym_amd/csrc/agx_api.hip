@@ -4,10 +4,13 @@
 // frame_skip x [build kernel, solve kernel] + finish kernel per chunk of environments.
 #include "agx_wave.h"
 #include "agx_variant.h"
+#include "agx_render.h"
+#include "agx_hull.h"
 #include "../../include/agx_blob.h"
 #include "../../include/agx.h"
 
 #include <dlfcn.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -127,6 +130,13 @@ void agx_launch_ee_pose(hipStream_t st, const uint32_t* blob, const float* state
 void agx_launch_ee_ik(hipStream_t st, const uint32_t* blob, const float* state, int sw, int n_envs, int arms, const float* target, int target_stride,
                       int frame, int iters, float damping, float gain, float* q_out, float* action, int action_stride, float* err);
 
+// the camera of a handle (agx_camera_set): the device tables of csrc/agx_render.hip, owned, and the arguments every agx_render passes
+struct agx_camera_s {
+  agx_render_args A;
+  float* frames; agx_render_coll* coll; float4* planes; float* colours;
+  int ncoll;
+};
+
 struct agx_handle_s {
   const agx_variant* V;   // the compiled kernel variant serving this model
   // what every launch passes: the model blob, the state / scratch records, their strides (agx_variant.h); with a cloth section (DressingBaxter) the
@@ -144,6 +154,7 @@ struct agx_handle_s {
   bool particles;       // the "cloth" section holds the water particles of the drinking scene (AGX_CL_PARTICLES), not a garment
   const float* cloth_pool_dev;   // the garments of the reset pool (agx_set_cloth_pool)
   bool can_sample;      // the variant has a reset generator (agx_reset.h) and the blob fits it
+  int ncoll;            // colliders of the model (agx_collider_count)
   int ee_arms;          // arm chains agx_ee_pose / agx_ee_ik serve (agx_ee_arms): 0 for a robot on wheels or a chain that fails arm_chain_ok
   // staging for the *_host convenience calls
   float *act_dev, *obs_dev, *rew_dev, *info_dev; uint8_t* done_dev;
@@ -157,6 +168,7 @@ struct agx_handle_s {
   int reset_flags;      // AGX_X_FLAGS of the blob's reset section (0 without one)
   agx_handle_s* settle; // bed bathing (AGX_X_FLAGS bit 4): the handle of the rag-doll model whose settled records the sampler reads (agx_attach_settle_model; not owned)
   int settle_substeps;  // substeps of that settle (100 simulation steps: bed_bathing.py:130-131)
+  agx_camera_s* cam;    // null until agx_camera_set
 };
 
 static void forget_warm(agx_handle_s* h, const uint8_t* mask_dev, hipStream_t st) {
@@ -250,6 +262,7 @@ int agx_create(const void* blob, size_t blob_bytes, int n_envs, int device, agx_
 static int create_fill(agx_handle h, const void* blob, size_t blob_bytes, int n_envs, int device) {
   const int32_t* hi = (const int32_t*)blob; const agx_variant* V = h->V; const bool can_sample = h->can_sample;
   h->iter_word = hi[AGX_H_S_ENV] + AGX_E_ITERATION;
+  h->ncoll = hi[AGX_H_NCOLL];
   h->device = device; h->L.n_envs = n_envs; h->L.act_dim = hi[AGX_H_ACT_DIM]; h->L.obs_dim = hi[AGX_H_OBS_DIM]; h->L.sw = hi[AGX_H_STATE_WORDS];
   HIPCHK(hipMalloc(&h->L.blob, blob_bytes));
   HIPCHK(hipMemcpy(h->L.blob, blob, blob_bytes, hipMemcpyHostToDevice));
@@ -311,6 +324,7 @@ void agx_destroy(agx_handle h) {
   hipFree(h->L.scratch); hipFree(h->L.overflow); hipFree(h->first_restart_dev); hipFree(h->L.chosen); hipFree(h->work_dev); hipFree(h->L.blob); hipFree(h->L.state); hipFree(h->L.episode); hipFree(h->act_dev); hipFree(h->obs_dev);
   hipFree(h->rew_dev); hipFree(h->info_dev); hipFree(h->done_dev);
   if (h->L.cloth) { hipFree(h->L.cloth); hipFree(h->L.trace); hipFree(h->L.report); }
+  if (h->cam) { hipFree(h->cam->frames); hipFree(h->cam->coll); hipFree(h->cam->planes); hipFree(h->cam->colours); delete h->cam; }
   if (h->ev0) hipEventDestroy(h->ev0); if (h->ev1) hipEventDestroy(h->ev1);      // a handle whose creation failed half way holds nulls
   for (int c = 0; c < 8; c++) for (int k = 0; k < 16; k++) if (h->kev[c][k]) hipEventDestroy(h->kev[c][k]);
   if (h->fork_ev) hipEventDestroy(h->fork_ev);
@@ -701,6 +715,133 @@ int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int fram
   HIPCHK(hipSetDevice(h->device));
   agx_launch_ee_ik((hipStream_t)stream, h->L.blob, h->L.state, h->L.sw, h->L.n_envs, h->ee_arms, target_dev, target_stride, frame, iters, damping, gain,
                    q_out_dev, action_dev, action_stride, err_dev);
+  HIPCHK(hipGetLastError());
+  return AGX_OK;
+}
+
+// ---- the camera (csrc/agx_render.hip, csrc/agx_hull.h): every check before any launch
+int agx_camera_colours(float* out36) {
+  if (!out36) return fail(AGX_E_ARG, "agx_camera_colours: null");
+  memcpy(out36, AGX_COLOURS, sizeof AGX_COLOURS);
+  return AGX_OK;
+}
+int agx_collider_count(agx_handle h, int* ncoll) {
+  if (!h || !ncoll) return fail(AGX_E_ARG, "agx_collider_count: bad argument");
+  *ncoll = h->ncoll; return AGX_OK;
+}
+int agx_collider_frames(agx_handle h, int env0, int count, float* frames_dev, void* stream) {
+  if (!h) return fail(AGX_E_ARG, "agx_collider_frames: null handle");
+  if (!frames_dev) return fail(AGX_E_ARG, "agx_collider_frames: null output");
+  if (env0 < 0 || count < 1 || count > h->L.n_envs || env0 > h->L.n_envs - count) return fail(AGX_E_ARG, "agx_collider_frames: [env0, env0 + count) is not a range of the handle's environments");
+  HIPCHK(hipSetDevice(h->device));
+  h->V->collider_frames(h->L, (hipStream_t)stream, env0, count, frames_dev);
+  HIPCHK(hipGetLastError());
+  return AGX_OK;
+}
+// the tables of a handle's first camera: per collider the face planes of its hull (none for a sphere or a capsule), the genders that see it and
+// its bounding radius; the frame table
+static int camera_build(agx_handle h) {
+  int32_t hdr[AGX_H_COUNT];
+  HIPCHK(hipMemcpy(hdr, h->L.blob, sizeof hdr, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> words((size_t)hdr[AGX_H_NWORDS]);
+  HIPCHK(hipMemcpy(words.data(), h->L.blob, words.size() * 4, hipMemcpyDeviceToHost));
+  const int32_t* bi = (const int32_t*)words.data(); const float* bf = (const float*)words.data();
+  const int ncoll = bi[AGX_H_NCOLL];
+  const int npart = h->particles ? h->cloth_nn : 0;
+  if (ncoll + npart > AGX_RENDER_LIST) return fail(AGX_E_LIMIT, "agx_camera_set: more than 1,024 colliders and particles");
+  std::vector<agx_render_coll> coll((size_t)ncoll);
+  std::vector<float4> planes;
+  for (int c = 0; c < ncoll; c++) coll[c].genders = 3;
+  // a human collider is drawn for one gender only where the pair table says so: the B range of a group that has a female alternative is the
+  // male human's, the alternative the female's; a group that exists for one gender only (flag bits 3, 4) names that gender's human colliders
+  for (int g = 0; g < bi[AGX_H_NGROUP]; g++) {
+    const int32_t* G = bi + bi[AGX_H_OFF_GROUP] + g * AGX_G_STRIDE;
+    auto only = [&](int c0, int c1, int bits) { for (int c = c0 < 0 ? 0 : c0; c < c1 && c < ncoll; c++) if (bi[bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE + AGX_C_TAG] == AGX_TAG_HUMAN) coll[c].genders &= bits; };
+    if (G[AGX_G_B0F] >= 0) { only(G[AGX_G_B0], G[AGX_G_B1], 1); only(G[AGX_G_B0F], G[AGX_G_B1F], 2); }
+    for (int s = 0; s < 2; s++) if (G[AGX_G_FLAGS] & (8 << s)) { only(G[AGX_G_A0], G[AGX_G_A1], 1 << s); only(G[AGX_G_B0], G[AGX_G_B1], 1 << s); }
+  }
+  std::vector<agxhull::Plane> pl;
+  for (int c = 0; c < ncoll; c++) {
+    const int32_t* Ci = bi + bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE; const float* Cf = (const float*)Ci;
+    const int nv = Ci[AGX_C_NVERT]; const float* V = bf + bi[AGX_H_OFF_VERT] + 3 * Ci[AGX_C_VOFF];
+    const double centre[3] = {Cf[AGX_C_AABB_C], Cf[AGX_C_AABB_C + 1], Cf[AGX_C_AABB_C + 2]}, rad = Cf[AGX_C_RADIUS];
+    coll[c].plane0 = (int)planes.size(); coll[c].nplane = 0;
+    double bound = 0;
+    if (nv <= 2) {
+      for (int k = 0; k < nv; k++) { double d = 0; for (int a = 0; a < 3; a++) d += (V[3 * k + a] - centre[a]) * (V[3 * k + a] - centre[a]); if (sqrt(d) > bound) bound = sqrt(d); }
+      bound += rad;
+    } else {
+      agxhull::hull_planes(V, nv, pl);
+      coll[c].nplane = (int)pl.size();
+      for (const agxhull::Plane& p : pl) planes.push_back(make_float4((float)p.n[0], (float)p.n[1], (float)p.n[2], (float)(p.off + rad - (p.n[0] * centre[0] + p.n[1] * centre[1] + p.n[2] * centre[2]))));
+      bound = agxhull::grown_bound(pl, rad, centre);
+    }
+    coll[c].bound = bound < 1e30 ? (float)(bound * (1.0 + 1e-6)) : 1e30f;
+  }
+  agx_camera_s* cam = new agx_camera_s();
+  memset(cam, 0, sizeof *cam);
+  h->cam = cam;      // from here on agx_destroy releases it
+  cam->ncoll = ncoll;
+  HIPCHK(hipMalloc(&cam->frames, (size_t)h->L.n_envs * (ncoll > 0 ? ncoll : 1) * 12 * 4));
+  HIPCHK(hipMalloc(&cam->coll, (coll.size() ? coll.size() : 1) * sizeof(agx_render_coll)));
+  HIPCHK(hipMalloc(&cam->planes, (planes.size() ? planes.size() : 1) * sizeof(float4)));
+  HIPCHK(hipMalloc(&cam->colours, sizeof AGX_COLOURS));
+  if (coll.size()) HIPCHK(hipMemcpy(cam->coll, coll.data(), coll.size() * sizeof(agx_render_coll), hipMemcpyHostToDevice));
+  if (planes.size()) HIPCHK(hipMemcpy(cam->planes, planes.data(), planes.size() * sizeof(float4), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(cam->colours, AGX_COLOURS, sizeof AGX_COLOURS, hipMemcpyHostToDevice));
+  agx_render_args& A = cam->A;
+  A.blob = h->L.blob; A.state = h->L.state; A.sw = h->L.sw; A.frames = cam->frames; A.coll = cam->coll; A.planes = cam->planes; A.colours = cam->colours;
+  if (npart) {
+    const int oc = bi[AGX_H_OFF_CLOTH];
+    A.water = h->L.cloth; A.cloth_words = h->L.cloth_words; A.npart = npart; A.part_radius = bf[oc + bi[oc + AGX_CL_OFF_PARAM] + AGX_CP_MARGIN];
+  }
+  return AGX_OK;
+}
+int agx_camera_set(agx_handle h, const float* eye3, const float* target3, const float* up3, float fov_deg, int width, int height, float near_plane, float far_plane) {
+  if (!h) return fail(AGX_E_ARG, "agx_camera_set: null handle");
+  if (!eye3 || !target3 || !up3) return fail(AGX_E_ARG, "agx_camera_set: null eye, target or up vector");
+  for (int k = 0; k < 3; k++) if (!isfinite(eye3[k]) || !isfinite(target3[k]) || !isfinite(up3[k])) return fail(AGX_E_ARG, "agx_camera_set: a view vector is not finite");
+  if (!(fov_deg > 0.f && fov_deg < 180.f)) return fail(AGX_E_ARG, "agx_camera_set: fov outside (0, 180) degrees");
+  if (width < 1 || width > 8192 || height < 1 || height > 8192) return fail(AGX_E_ARG, "agx_camera_set: width or height outside 1..8192");
+  if (!(near_plane > 0.f) || !(far_plane > near_plane) || !isfinite(far_plane)) return fail(AGX_E_ARG, "agx_camera_set: near and far must satisfy 0 < near < far");
+  // p.computeViewMatrix: f = unit(target - eye), s = unit(f x up), u = s x f
+  double f[3], s[3], u[3], l = 0;
+  for (int k = 0; k < 3; k++) { f[k] = (double)target3[k] - (double)eye3[k]; l += f[k] * f[k]; }
+  if (!(l > 0)) return fail(AGX_E_ARG, "agx_camera_set: eye and target are the same point");
+  for (int k = 0; k < 3; k++) f[k] /= sqrt(l);
+  s[0] = f[1] * up3[2] - f[2] * up3[1]; s[1] = f[2] * up3[0] - f[0] * up3[2]; s[2] = f[0] * up3[1] - f[1] * up3[0];
+  l = s[0] * s[0] + s[1] * s[1] + s[2] * s[2];
+  if (!(l > 1e-24)) return fail(AGX_E_ARG, "agx_camera_set: the up vector lies along the view direction");
+  for (int k = 0; k < 3; k++) s[k] /= sqrt(l);
+  u[0] = s[1] * f[2] - s[2] * f[1]; u[1] = s[2] * f[0] - s[0] * f[2]; u[2] = s[0] * f[1] - s[1] * f[0];
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->cam) { const int rc = camera_build(h); if (rc) return rc; }
+  agx_render_args& A = h->cam->A;
+  for (int k = 0; k < 3; k++) { A.eye[k] = eye3[k]; A.right[k] = (float)s[k]; A.up[k] = (float)u[k]; A.fwd[k] = (float)f[k]; }
+  A.ty = (float)tan(0.5 * (double)fov_deg * M_PI / 180.0); A.tx = (float)((double)width / (double)height * tan(0.5 * (double)fov_deg * M_PI / 180.0));
+  A.width = width; A.height = height; A.near = near_plane; A.far = far_plane;
+  return AGX_OK;
+}
+int agx_render(agx_handle h, int env0, int count, const float* light3, float ambient, float diffuse, float* depth_dev, int32_t* seg_dev, uint8_t* rgba_dev, void* stream) {
+  if (!h) return fail(AGX_E_ARG, "agx_render: null handle");
+  if (!h->cam || h->cam->A.width == 0) return fail(AGX_E_ARG, "agx_render: no camera; call agx_camera_set first");
+  if (env0 < 0 || count < 1 || count > h->L.n_envs || env0 > h->L.n_envs - count) return fail(AGX_E_ARG, "agx_render: [env0, env0 + count) is not a range of the handle's environments");
+  if (count > 65535) return fail(AGX_E_ARG, "agx_render: more than 65535 environments in one call");
+  if (!light3) return fail(AGX_E_ARG, "agx_render: null light vector");
+  double l = 0; for (int k = 0; k < 3; k++) l += (double)light3[k] * (double)light3[k];
+  if (!isfinite(l) || !(l > 0)) return fail(AGX_E_ARG, "agx_render: the light vector is zero or not finite");
+  if (!isfinite(ambient) || !isfinite(diffuse)) return fail(AGX_E_ARG, "agx_render: ambient or diffuse is not finite");
+  if (!depth_dev && !seg_dev && !rgba_dev) return fail(AGX_E_ARG, "agx_render: all three outputs are null");
+  if ((uintptr_t)rgba_dev & 3) return fail(AGX_E_ARG, "agx_render: rgba_dev is not 4-byte aligned");
+  HIPCHK(hipSetDevice(h->device));
+  agx_camera_s* cam = h->cam;
+  h->V->collider_frames(h->L, (hipStream_t)stream, env0, count, cam->frames + (size_t)env0 * cam->ncoll * 12);
+  HIPCHK(hipGetLastError());
+  agx_render_args A = cam->A;
+  for (int k = 0; k < 3; k++) A.light[k] = (float)((double)light3[k] / sqrt(l));
+  A.ambient = ambient; A.diffuse = diffuse; A.env0 = env0;
+  A.depth = depth_dev; A.seg = seg_dev; A.rgba = (uint32_t*)rgba_dev;
+  agx_launch_render((hipStream_t)stream, A, count);
   HIPCHK(hipGetLastError());
   return AGX_OK;
 }

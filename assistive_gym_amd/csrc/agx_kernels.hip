@@ -167,6 +167,22 @@ AGX_K(agx_reset_verdict_kernel)(const uint32_t* __restrict__ blob, const float* 
   if ((!active || active[env]) && chosen[env] >= 0) again = agx::reset_collides(blob, scratch + (size_t)env * agx::SCR_WORDS, (int)threadIdx.x);
   if (threadIdx.x == 0) { work[env] = again ? 1 : 0; if (again) first_restart[env] = chosen[env] + 1; }
 }
+// the camera's stage A (agx_collider_frames, agx_render; the ray caster is csrc/agx_render.hip): the world frame of every collider's body --
+// position (3), rotation (9, row-major) -- of the environments [env0, env0 + gridDim.x) into frames[blockIdx.x][ncoll][12].  The state is read only.
+extern "C" __global__ void __launch_bounds__(64, 2)
+AGX_K(agx_frames_kernel)(const uint32_t* __restrict__ blob, const float* __restrict__ state, float* __restrict__ frames, int env0, int n_envs, int sw) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int env = env0 + blockIdx.x;
+  if (env >= n_envs) return;
+  agx::Ctx c; agx::ctx_init(c, blob, lds, (int)threadIdx.x);
+  agx::load_env(c, state + (size_t)env * sw, sw);
+  agx::kinematics(c);
+  float* out = frames + (size_t)blockIdx.x * c.ncoll * 12;
+  for (int col = (int)threadIdx.x; col < c.ncoll; col += 64) {
+    m3 R; v3 p; agx::body_xf(c, CLI(c, col, AGX_C_BODY), R, p);
+    st3(out + 12 * col, p); stm3(out + 12 * col + 3, R);
+  }
+}
 
 // LDS of a solve launch.  AGX_SOLVE_LDS_BYTES (tuning knob, read once): the row-local sweeps (agx_pgs_lvw.h, agx_pgs_lvs.h) size their window of resident
 // rows from it -- more LDS = fewer rows streamed from L2, fewer wavefronts per CU; never below what the other sweeps and solve_tail() need
@@ -182,6 +198,7 @@ hipError_t v_init(void) {
 #endif
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_finish_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, agx::LDS_BYTES);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_observe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, agx::LDS_BYTES);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_frames_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, agx::LDS_BYTES);
 #if AGX_TASK == 3
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)AGX_K(agx_cloth_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #endif
@@ -223,6 +240,9 @@ void v_verdict(const agx_launch& L, hipStream_t st, const uint8_t* active, uint8
 void v_collision_flags(const agx_launch& L, hipStream_t st, uint8_t* flags) {
   hipLaunchKernelGGL(AGX_K(agx_collision_flags_kernel), dim3(L.n_envs), dim3(64), 0, st, L.blob, L.scratch, flags, L.n_envs);
 }
+void v_frames(const agx_launch& L, hipStream_t st, int e0, int ne, float* frames) {
+  hipLaunchKernelGGL(AGX_K(agx_frames_kernel), dim3(ne), dim3(64), agx::LDS_BYTES, st, L.blob, L.state, frames, e0, L.n_envs, L.sw);
+}
 
 #define AGX_STR2_(x) #x
 #define AGX_STR_(x) AGX_STR2_(x)
@@ -252,7 +272,8 @@ const agx_variant g_variant = {
 #else
   nullptr,
 #endif
-  agx::SCR_O_META + agx::META_NWARM
+  agx::SCR_O_META + agx::META_NWARM,
+  v_frames
 };
 
 }  // namespace

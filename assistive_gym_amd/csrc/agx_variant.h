@@ -59,6 +59,8 @@ struct agx_variant {
   // word of the per-environment scratch record that counts the entries of the warm-start memory (AGX_P_WARMSTART): agx_api.hip zeroes it
   // for every environment whose state is replaced from outside (set_state, resets)
   int scr_warm_word;
+  // the camera's stage A: frames[k][ncoll][12] = position and rotation of the body of every collider of environment e0 + k, k < ne
+  void (*collider_frames)(const agx_launch& L, hipStream_t st, int e0, int ne, float* frames);
 };
 
 // one accessor per line of agx_variants.def: agx_variant_<name>()

@@ -15,7 +15,8 @@ EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_p
            'agx_set_state', 'agx_get_state', 'agx_state_dev', 'agx_settle', 'agx_settle_debug', 'agx_cloth_nodes', 'agx_set_cloth', 'agx_get_cloth', 'agx_cloth_dev', 'agx_set_cloth_pool', 'agx_get_cloth_report', 'agx_step', 'agx_step_debug', 'agx_step_timed', 'agx_debug_words',
            'agx_observe', 'agx_observe_masked', 'agx_reset_done_at', 'agx_sample_reset', 'agx_reset', 'agx_attach_settle_model', 'agx_reset_done', 'agx_step_host', 'agx_observe_host', 'agx_profile_begin', 'agx_profile_end',
            'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_chunk_count', 'agx_set_env_offset', 'agx_check_collisions',
-           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae', 'agx_ee_arms', 'agx_ee_pose', 'agx_ee_ik']
+           'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae', 'agx_ee_arms', 'agx_ee_pose', 'agx_ee_ik',
+           'agx_camera_set', 'agx_render', 'agx_collider_count', 'agx_collider_frames', 'agx_camera_colours']
 
 
 class AgxError(RuntimeError):
@@ -37,6 +38,11 @@ def load():
         L.agx_ee_arms.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.agx_ee_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.agx_ee_ik.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.agx_camera_set.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float]
+        L.agx_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.agx_collider_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.agx_collider_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.agx_camera_colours.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -90,6 +96,13 @@ def gae(rewards, values, dones, gamma, lam, adv, ret, stream=0):
     T, N = rewards.shape
     assert values.shape == (T + 1, N) and dones.shape == (T, N) and all(x.is_contiguous() for x in (rewards, values, dones, adv, ret))
     _check_stateless(load().agx_gae(rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), T, N, gamma, lam, adv.data_ptr(), ret.data_ptr(), stream or None), 'agx_gae')
+
+
+def camera_colours():
+    """agx_camera_colours: the camera's colour table, float32 [12, 3] -- collider tags 0..9 (AGX_TAG_*), the water particles, the background"""
+    out = np.zeros((12, 3), dtype=np.float32)
+    check(load().agx_camera_colours(out.ctypes.data_as(C.c_void_p)), 'agx_camera_colours')
+    return out
 
 
 def _ptr(x):
@@ -256,6 +269,31 @@ class Stepper:
         check(self.L.agx_ee_ik(self.h, target.data_ptr(), target.stride(0), self.EE_FRAMES[frame], int(iters), float(damping), float(gain),
                                q_out.data_ptr() if q_out is not None else None, action.data_ptr() if action is not None else None,
                                action.stride(0) if action is not None else 0, err.data_ptr() if err is not None else None, stream or None), 'agx_ee_ik')
+
+    # ---- the camera (agx_camera_set / agx_render / agx_collider_frames, include/agx.h)
+    def collider_count(self):
+        out = C.c_int()
+        check(self.L.agx_collider_count(self.h, C.byref(out)), 'agx_collider_count')
+        return out.value
+
+    def collider_frames(self, out, env0=0, stream=0):
+        """out: contiguous float32 device tensor [count, ncoll, 12] <- world position (3) and rotation (9, row-major) of the body of every collider of
+        the environments [env0, env0 + count)"""
+        assert out.is_contiguous() and out.dim() == 3 and tuple(out.shape[1:]) == (self.collider_count(), 12)
+        check(self.L.agx_collider_frames(self.h, int(env0), int(out.shape[0]), out.data_ptr(), stream or None), 'agx_collider_frames')
+
+    def camera_set(self, eye, target, up=(0.0, 0.0, 1.0), fov=60.0, width=480, height=270, near=0.01, far=100.0):
+        """one camera for all environments of the stepper: the view of p.computeViewMatrix(eye, target, up), vertical field of view in degrees"""
+        v = [np.ascontiguousarray(x, dtype=np.float32).reshape(3) for x in (eye, target, up)]
+        check(self.L.agx_camera_set(self.h, v[0].ctypes.data, v[1].ctypes.data, v[2].ctypes.data, float(fov), int(width), int(height), float(near), float(far)), 'agx_camera_set')
+
+    def render(self, env0, count, light=(0.0, -3.0, 1.0), ambient=0.8, diffuse=0.3, depth=None, seg=None, rgba=None, stream=0):
+        """agx_render of the environments [env0, env0 + count) into contiguous device tensors [count, height, width] -- depth float32, seg int32 --
+        and rgba uint8 [count, height, width, 4]; any of them may be None"""
+        assert all(x is None or x.is_contiguous() for x in (depth, seg, rgba))
+        l = np.ascontiguousarray(light, dtype=np.float32).reshape(3)
+        check(self.L.agx_render(self.h, int(env0), int(count), l.ctypes.data, float(ambient), float(diffuse), depth.data_ptr() if depth is not None else None,
+                                seg.data_ptr() if seg is not None else None, rgba.data_ptr() if rgba is not None else None, stream or None), 'agx_render')
 
     def settle(self, n_substeps, stream=0):
         check(self.L.agx_settle(self.h, C.c_int(n_substeps), C.c_void_p(stream)), 'agx_settle')

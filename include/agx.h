@@ -231,6 +231,40 @@ int agx_ee_pose(agx_handle h, float* pose_dev, void* stream);
 int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int frame, int iters, float damping, float gain,
               float* q_out_dev, float* action_dev, int action_stride, float* err_dev, void* stream);
 
+/* ---- the camera: depth, segmentation and RGB images of the environments, ray-cast on the device (csrc/agx_render.hip).  The reference's
+ * env.setup_camera / setup_camera_rpy / get_camera_image_depth (assistive_gym/envs/env.py:342-359) hand a view to PyBullet's renderer; here ONE
+ * camera is shared by all environments of a handle (every scene sits at the same world coordinates) and what is drawn is the collision geometry
+ * of the model blob: every collider by its vertex count -- 1 a sphere, 2 a capsule, 3 and more the convex polytope of the vertices with each face
+ * plane pushed outward by AGX_C_RADIUS (a flat or degenerate vertex set: its bounding box) -- for the environment's gender only, where the
+ * collide phase places it (a food or water particle the task has retired sits beyond the far plane), and the water particles of a drinking scene as
+ * spheres of the section's MARGIN.  The garment of a dressing scene is NOT drawn.  Not Bullet's rasteriser: no visual meshes, no textures,
+ * no shadows, no specular term.
+ * Pixel (i, j), row 0 at the top, casts one ray through its centre: in camera space ((2 (i + 0.5) / w - 1) aspect tan(fov / 2),
+ * (1 - 2 (j + 0.5) / h) tan(fov / 2), -1), not normalised, so the ray parameter t is the view-space depth.  A convex collider meets the ray in an
+ * interval; its hit is where the ray enters, or where it leaves if it enters before the near plane.  The nearest hit with near <= t <= far wins,
+ * the lower collider index on a tie.
+ *
+ * agx_camera_set: the view from (eye, target, up) as p.computeViewMatrix builds it, fov_deg the vertical field of view, aspect = width / height
+ * (the reference: up = [0, 0, 1], near 0.01, far 100).  The first call on a handle also builds the hulls' face planes on the host and allocates the
+ * frame table; later calls only move the camera.
+ * agx_render: environments [env0, env0 + count), count <= 65535, into [count][height][width] device arrays, each of which may be NULL (not all):
+ *   depth_dev float32: t of the hit, `far` where nothing is hit;
+ *   seg_dev   int32:   the collider index, ncoll + k for water particle k, -1 for the background;
+ *   rgba_dev  uint8[4] (4-byte aligned): round(255 min(1, colour (ambient + diffuse max(0, n . l)))) per channel, l = light3 normalised (the
+ *             direction towards the light), n the outward normal at the hit, colour by the collider's AGX_C_TAG from the table agx_camera_colours
+ *             copies out (float[12][3]: tags 0..9, then the water, then the background, which is not shaded); alpha 255.
+ * agx_collider_count / agx_collider_frames: the kinematics half on its own -- frames_dev[count][ncoll][12] = world position (3) and rotation
+ * (9, row-major) of the body of every collider.  Nothing here writes the state records.
+ * AGX_E_ARG with agx_last_error text, before any launch: a NULL handle or view vector, values that are not finite, fov outside (0, 180), width /
+ * height outside 1..8192, near <= 0 or far <= near, eye = target or up along the view direction, agx_render before agx_camera_set, a range
+ * outside the handle's environments, a zero light vector, all three outputs NULL.  AGX_E_LIMIT: more than 1,024 colliders + particles. */
+int agx_camera_set(agx_handle h, const float* eye3, const float* target3, const float* up3, float fov_deg, int width, int height, float near_plane, float far_plane);
+int agx_render(agx_handle h, int env0, int count, const float* light3, float ambient, float diffuse,
+               float* depth_dev, int32_t* seg_dev, uint8_t* rgba_dev, void* stream);
+int agx_collider_count(agx_handle h, int* ncoll);
+int agx_collider_frames(agx_handle h, int env0, int count, float* frames_dev, void* stream);
+int agx_camera_colours(float* out36);
+
 /* convenience wrappers with HOST buffers (copies included; not the timed path) */
 int agx_step_host(agx_handle h, const float* actions, float* obs, float* reward, uint8_t* done, float* info);
 int agx_observe_host(agx_handle h, float* obs);
