@@ -4,8 +4,10 @@
 The reference's env.setup_camera / setup_camera_rpy / get_camera_image_depth (assistive_gym/envs/env.py:342-359) hand a view to PyBullet's renderer.
 Here one camera is shared by all environments -- every scene sits at the same world coordinates -- and what is drawn is the COLLISION geometry of the
 model blob: spheres, capsules and convex hulls (their face planes pushed outward by the collider's radius), coloured by the collider's tag, plus the
-water particles of a drinking scene.  Not drawn: visual meshes and textures, the garment of a dressing scene, shadows, a specular term.  The images
-are not PyBullet's pixel for pixel.
+water particles of a drinking scene and, where it is switched on (garment=True / set_garment; off by default), the garment of a dressing scene:
+its triangles at their current node positions, both sides visible, flat shaded in the gown's own colour (139, 195, 74) / 256, opaque; face f has
+the segmentation value collider count + f (Stepper.garment_faces).  Not drawn: visual meshes and textures, shadows, a specular term, the gown's
+translucency.  The images are not PyBullet's pixel for pixel.
 
 The view conventions live here, once: view_from_eye / view_from_rpy (PyBullet's computeViewMatrix / computeViewMatrixFromYawPitchRoll with the
 z axis up), pixel_rays (the ray of a pixel) and bullet_depth (the depth buffer PyBullet returns for a metric depth)."""
@@ -56,12 +58,16 @@ def bullet_depth(z, near=NEAR, far=FAR):
 
 def collider_info(blob, index):
     """what a value of the segmentation image stands for: (tag, body code, link) of collider `index` -- AGX_C_TAG, AGX_C_BODY, AGX_C_LINK of
-    include/agx_blob.h -- ('water', k, -1) for particle k of a drinking scene (index = collider count + k), None for the background (-1)"""
+    include/agx_blob.h -- ('water', k, -1) for particle k of a drinking scene (index = collider count + k), ('garment', f, -1) for face f of the
+    garment of a dressing scene (index = collider count + f), None for the background (-1)"""
     ncoll = blob.h['NCOLL']
     if index < 0:
         return None
     if index >= ncoll:
-        return ('water', int(index) - ncoll, -1)
+        from .model import compiler as L
+        oc = blob.h.get('OFF_CLOTH', 0)
+        garment = bool(oc) and not int(blob.i[oc + L.CL['PARTICLES']])
+        return ('garment' if garment else 'water', int(index) - ncoll, -1)
     c = blob.collider(int(index))
     return (c['tag'], c['body'], c['link'])
 
@@ -70,15 +76,24 @@ class BatchedCamera:
     """camera = BatchedCamera(env, 64, 48); images = camera.render()        # every environment
     images = camera.render(range(16))                                       # a subset (a contiguous range is one launch)
     -> dict(depth float32 [n, h, w] metric view-space depth, `far` where nothing is hit; seg int32 [n, h, w] collider index (collider_info), -1 =
-    background; rgba uint8 [n, h, w, 4]), torch tensors in the GPU's memory.  env: a vec env (its .stepper) or a Stepper."""
+    background; rgba uint8 [n, h, w, 4]), torch tensors in the GPU's memory.  env: a vec env (its .stepper) or a Stepper.
+    garment=True draws the garment of a dressing scene (seg = collider count + face); a scene without one raises."""
 
     def __init__(self, env, width=1920 // 4, height=1080 // 4, camera_eye=DEFAULT_EYE, camera_target=DEFAULT_TARGET, fov=DEFAULT_FOV,
-                 light_pos=DEFAULT_LIGHT, ambient=DEFAULT_AMBIENT, diffuse=DEFAULT_DIFFUSE):
+                 light_pos=DEFAULT_LIGHT, ambient=DEFAULT_AMBIENT, diffuse=DEFAULT_DIFFUSE, garment=False):
         self.stepper = getattr(env, 'stepper', env)
         self.blob = self.stepper.blob
         self.width, self.height = int(width), int(height)
         self.light_pos, self.ambient, self.diffuse = tuple(light_pos), float(ambient), float(diffuse)
         self.setup(camera_eye, camera_target, fov)
+        self.garment = False
+        if garment:
+            self.set_garment(True)
+
+    def set_garment(self, on=True):
+        """draw the garment of a dressing scene, or stop drawing it (agx_camera_garment)"""
+        self.stepper.camera_garment(on)
+        self.garment = bool(on)
 
     def setup(self, camera_eye=DEFAULT_EYE, camera_target=DEFAULT_TARGET, fov=DEFAULT_FOV, up=(0.0, 0.0, 1.0)):
         """env.setup_camera (env.py:342-346)"""

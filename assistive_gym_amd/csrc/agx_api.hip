@@ -6,6 +6,7 @@
 #include "agx_variant.h"
 #include "agx_render.h"
 #include "agx_hull.h"
+#include "agx_garment.h"
 #include "../../include/agx_blob.h"
 #include "../../include/agx.h"
 
@@ -135,6 +136,9 @@ struct agx_camera_s {
   agx_render_args A;
   float* frames; agx_render_coll* coll; float4* planes; float* colours;
   int ncoll;
+  int4* tris; int ntri;      // the garment's triangle table (csrc/agx_garment.h), null until agx_camera_garment first switches the garment on
+  bool garment;              // the switch of agx_camera_garment
+  float* lend_depth; int* lend_seg; size_t lend_pixels;      // images the garment kernel merges into where the caller asked for no depth or seg
 };
 
 struct agx_handle_s {
@@ -324,7 +328,7 @@ void agx_destroy(agx_handle h) {
   hipFree(h->L.scratch); hipFree(h->L.overflow); hipFree(h->first_restart_dev); hipFree(h->L.chosen); hipFree(h->work_dev); hipFree(h->L.blob); hipFree(h->L.state); hipFree(h->L.episode); hipFree(h->act_dev); hipFree(h->obs_dev);
   hipFree(h->rew_dev); hipFree(h->info_dev); hipFree(h->done_dev);
   if (h->L.cloth) { hipFree(h->L.cloth); hipFree(h->L.trace); hipFree(h->L.report); }
-  if (h->cam) { hipFree(h->cam->frames); hipFree(h->cam->coll); hipFree(h->cam->planes); hipFree(h->cam->colours); delete h->cam; }
+  if (h->cam) { hipFree(h->cam->frames); hipFree(h->cam->coll); hipFree(h->cam->planes); hipFree(h->cam->colours); hipFree(h->cam->tris); hipFree(h->cam->lend_depth); hipFree(h->cam->lend_seg); delete h->cam; }
   if (h->ev0) hipEventDestroy(h->ev0); if (h->ev1) hipEventDestroy(h->ev1);      // a handle whose creation failed half way holds nulls
   for (int c = 0; c < 8; c++) for (int k = 0; k < 16; k++) if (h->kev[c][k]) hipEventDestroy(h->kev[c][k]);
   if (h->fork_ev) hipEventDestroy(h->fork_ev);
@@ -785,10 +789,11 @@ static int camera_build(agx_handle h) {
   HIPCHK(hipMalloc(&cam->frames, (size_t)h->L.n_envs * (ncoll > 0 ? ncoll : 1) * 12 * 4));
   HIPCHK(hipMalloc(&cam->coll, (coll.size() ? coll.size() : 1) * sizeof(agx_render_coll)));
   HIPCHK(hipMalloc(&cam->planes, (planes.size() ? planes.size() : 1) * sizeof(float4)));
-  HIPCHK(hipMalloc(&cam->colours, sizeof AGX_COLOURS));
+  HIPCHK(hipMalloc(&cam->colours, sizeof AGX_COLOURS + sizeof AGX_GARMENT_COLOUR));
   if (coll.size()) HIPCHK(hipMemcpy(cam->coll, coll.data(), coll.size() * sizeof(agx_render_coll), hipMemcpyHostToDevice));
   if (planes.size()) HIPCHK(hipMemcpy(cam->planes, planes.data(), planes.size() * sizeof(float4), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(cam->colours, AGX_COLOURS, sizeof AGX_COLOURS, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(cam->colours + 3 * AGX_COLOUR_GARMENT, AGX_GARMENT_COLOUR, sizeof AGX_GARMENT_COLOUR, hipMemcpyHostToDevice));
   agx_render_args& A = cam->A;
   A.blob = h->L.blob; A.state = h->L.state; A.sw = h->L.sw; A.frames = cam->frames; A.coll = cam->coll; A.planes = cam->planes; A.colours = cam->colours;
   if (npart) {
@@ -835,14 +840,72 @@ int agx_render(agx_handle h, int env0, int count, const float* light3, float amb
   if ((uintptr_t)rgba_dev & 3) return fail(AGX_E_ARG, "agx_render: rgba_dev is not 4-byte aligned");
   HIPCHK(hipSetDevice(h->device));
   agx_camera_s* cam = h->cam;
+  if (cam->garment && (!depth_dev || !seg_dev)) {      // the garment kernel takes up a pixel's depth and segmentation value from the images
+    const size_t need = (size_t)count * cam->A.width * cam->A.height;
+    if (need > cam->lend_pixels) {      // (hipFree waits for the launches that still use the old buffers)
+      hipFree(cam->lend_depth); hipFree(cam->lend_seg); cam->lend_depth = nullptr; cam->lend_seg = nullptr; cam->lend_pixels = 0;
+      HIPCHK(hipMalloc(&cam->lend_depth, need * sizeof(float))); HIPCHK(hipMalloc(&cam->lend_seg, need * sizeof(int)));
+      cam->lend_pixels = need;
+    }
+  }
   h->V->collider_frames(h->L, (hipStream_t)stream, env0, count, cam->frames + (size_t)env0 * cam->ncoll * 12);
   HIPCHK(hipGetLastError());
   agx_render_args A = cam->A;
   for (int k = 0; k < 3; k++) A.light[k] = (float)((double)light3[k] / sqrt(l));
   A.ambient = ambient; A.diffuse = diffuse; A.env0 = env0;
   A.depth = depth_dev; A.seg = seg_dev; A.rgba = (uint32_t*)rgba_dev;
-  agx_launch_render((hipStream_t)stream, A, count);
+  if (cam->garment) { if (!A.depth) A.depth = cam->lend_depth; if (!A.seg) A.seg = cam->lend_seg; }
+  agx_launch_render((hipStream_t)stream, A, count, cam->garment);
   HIPCHK(hipGetLastError());
+  return AGX_OK;
+}
+// ---- the garment of a dressing scene in the camera's images (csrc/agx_garment.h, the garment kernel of csrc/agx_render.hip)
+int agx_camera_garment_colour(float* out3) {
+  if (!out3) return fail(AGX_E_ARG, "agx_camera_garment_colour: null");
+  memcpy(out3, AGX_GARMENT_COLOUR, sizeof AGX_GARMENT_COLOUR);
+  return AGX_OK;
+}
+// the triangle table of the handle's model, from the blob as the device holds it; empty for a model without a garment
+static int garment_table(agx_handle h, const char* who, std::vector<int>& tris) {
+  tris.clear();
+  if (!h->L.cloth || h->particles) return AGX_OK;
+  HIPCHK(hipSetDevice(h->device));
+  int32_t hdr[AGX_H_COUNT];
+  HIPCHK(hipMemcpy(hdr, h->L.blob, sizeof hdr, hipMemcpyDeviceToHost));
+  std::vector<int32_t> words((size_t)hdr[AGX_H_NWORDS]);
+  HIPCHK(hipMemcpy(words.data(), h->L.blob, words.size() * 4, hipMemcpyDeviceToHost));
+  const char* what = "";
+  if (agxgarment::garment_faces(words.data(), words.size(), tris, &what) != 0 || (words[words[AGX_H_OFF_CLOTH] + AGX_CL_NN] != h->cloth_nn))
+    return fail(AGX_E_BLOB, (std::string(who) + ": malformed cloth section: " + what).c_str());
+  return AGX_OK;
+}
+int agx_garment_faces(agx_handle h, int* count, int* host_tris) {
+  if (!h) return fail(AGX_E_ARG, "agx_garment_faces: null handle");
+  if (!count) return fail(AGX_E_ARG, "agx_garment_faces: null count");
+  std::vector<int> tris;
+  const int rc = garment_table(h, "agx_garment_faces", tris); if (rc) return rc;
+  *count = (int)(tris.size() / 3);
+  if (host_tris && !tris.empty()) memcpy(host_tris, tris.data(), tris.size() * sizeof(int));
+  return AGX_OK;
+}
+int agx_camera_garment(agx_handle h, int on) {
+  if (!h) return fail(AGX_E_ARG, "agx_camera_garment: null handle");
+  if (on && (!h->L.cloth || h->particles)) return fail(AGX_E_ARG, "agx_camera_garment: this model has no garment (no cloth section, or the water particles of a drinking scene)");
+  if (!h->cam || h->cam->A.width == 0) return fail(AGX_E_ARG, "agx_camera_garment: no camera; call agx_camera_set first");
+  agx_camera_s* cam = h->cam;
+  if (on && !cam->tris) {      // the first enabling call: the table, as one 16-byte entry per face
+    std::vector<int> tris;
+    const int rc = garment_table(h, "agx_camera_garment", tris); if (rc) return rc;
+    const size_t n = tris.size() / 3;
+    std::vector<int4> packed(n);
+    for (size_t f = 0; f < n; f++) packed[f] = make_int4(tris[3 * f], tris[3 * f + 1], tris[3 * f + 2], 0);
+    int4* dev = nullptr;
+    HIPCHK(hipMalloc(&dev, (n ? n : 1) * sizeof(int4)));
+    if (n && hipMemcpy(dev, packed.data(), n * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dev); return fail(AGX_E_HIP, "agx_camera_garment: upload of the triangle table"); }
+    cam->tris = dev; cam->ntri = (int)n;
+    cam->A.tris = dev; cam->A.ntri = (int)n; cam->A.garment = h->L.cloth; cam->A.cloth_words = h->L.cloth_words;
+  }
+  cam->garment = on != 0;
   return AGX_OK;
 }
 

@@ -13,6 +13,7 @@
 //      lies before the near plane; the nearest hit within [near, far] wins, the lower index on a tie (the list is ascending, the test strict).
 //   3. Shade and write: 4-byte stores, consecutive lanes on consecutive pixels of a row.
 // The ray direction is not normalised -- its component along the view direction is 1 -- so the ray parameter is the view-space depth.
+// The garment of a dressing scene is drawn over these images by a second kernel on the same tiles, agx_render_garment_kernel below.
 #include "agx_wave.h"
 #include "agx_math.h"
 #include "agx_render.h"
@@ -196,7 +197,104 @@ agx_render_kernel(const agx_render_args A) {
   }
 }
 
-void agx_launch_render(hipStream_t st, const agx_render_args& A, int count) {
+// The garment of a dressing scene (agx_camera_garment), drawn over the images agx_render_kernel has left: the same tiles, wavefronts and rays.  A
+// kernel of its own and not a phase compiled into the rigid caster: a second instantiation of that kernel is scheduled and contracted differently
+// by the compiler, and its rigid pixels then differ in the last bits from the garment-off image (measured on the device); this way the rigid
+// caster is the same machine code whether the garment is drawn or not, and a pixel no face wins is not touched at all.
+//   1. A lane takes up its pixel's depth and segmentation value from the images (A.depth and A.seg are never null here: where the caller asked
+//      for neither, agx_render lends buffers of its own).
+//   2. Cull, 64 faces per round: a lane loads its face's node indices (one 16-byte entry of A.tris) and the three positions from the environment's
+//      garment record (47 KB per environment: the tiles of an environment are neighbours in the grid, so it stays in L2), makes them eye-relative
+//      and tests the box of their projection against the tile's box on the image plane; a face with a vertex before the near plane or behind the
+//      eye is kept without projecting, one wholly before the near plane or beyond the far plane is dropped.  Ballot + prefix count compact the
+//      survivors into the list in ascending order.
+//   3. Cast whenever the next round might not fit into the list, and after the last round: the entry is wave uniform, so the face's indices and
+//      nine coordinates come through scalar loads, once per wave.  Moeller-Trumbore on eye-relative vertices, the edges formed first, the triple
+//      products turned so that everything but three dot products with the ray is the same in every lane.  Ascending order and the strict test
+//      give the tie rule across flushes: a collider before a face, a lower face before a higher one.  Every comparison is false for a NaN: a face
+//      with a node that is not finite is never hit.
+//   4. A lane whose pixel a face has won writes depth, seg = ncoll + face and the shaded garment colour; the others write nothing.
+// Loop bounds come from counts (faces, ballot sums), never from the garment's data; no per-lane array is indexed dynamically.
+extern "C" __global__ void __launch_bounds__(64)
+agx_render_garment_kernel(const agx_render_args A) {
+  __shared__ int list[AGX_RENDER_LIST];
+  const int lane = (int)threadIdx.x;
+  const int ncoll = ((const int*)A.blob)[AGX_H_NCOLL];
+  const int tiles_x = (A.width + AGX_RENDER_TW - 1) / AGX_RENDER_TW;
+  const int x0 = ((int)blockIdx.x % tiles_x) * AGX_RENDER_TW, y0 = ((int)blockIdx.x / tiles_x) * AGX_RENDER_TH;
+  const int env = A.env0 + (int)blockIdx.y;
+  const float* X = A.garment + (size_t)env * A.cloth_words;
+  const v3 eye = mk3(A.eye[0], A.eye[1], A.eye[2]), right = mk3(A.right[0], A.right[1], A.right[2]), up = mk3(A.up[0], A.up[1], A.up[2]),
+           fwd = mk3(A.fwd[0], A.fwd[1], A.fwd[2]);
+  const float sx = 2.f * A.tx / (float)A.width, sy = 2.f * A.ty / (float)A.height;
+  const float near = A.near, far = A.far;
+  // the ray, exactly as the rigid caster forms it
+  const int px = x0 + (lane & (AGX_RENDER_TW - 1)), py = y0 + lane / AGX_RENDER_TW;
+  const float cx = ((float)px + 0.5f) * sx - A.tx, cy = A.ty - ((float)py + 0.5f) * sy;
+  const v3 dw = cx * right + cy * up + fwd;
+  const bool inside = px < A.width && py < A.height;
+  const size_t pix = ((size_t)blockIdx.y * A.height + (inside ? py : 0)) * A.width + (inside ? px : 0);
+  float best_t = inside && A.seg[pix] >= 0 ? A.depth[pix] : 3.0e38f;      // (the background's depth is `far`, which a face at t = far still beats)
+  int best = -1; v3 best_n = mk3(0.f, 0.f, 0.f);      // the face that has won this pixel, its unit normal towards the eye
+  // the tile's box on the image plane (camera space at depth 1); the pixel centres lie half a pixel inside it
+  const int x1 = x0 + AGX_RENDER_TW < A.width ? x0 + AGX_RENDER_TW : A.width, y1 = y0 + AGX_RENDER_TH < A.height ? y0 + AGX_RENDER_TH : A.height;
+  const float slack = 4e-5f;      // eye-relative coordinates carry 1e-7 m of rounding, projected from no nearer than the near plane's 0.01 m: 1e-5
+  const float ul = (float)x0 * sx - A.tx - slack, ur = (float)x1 * sx - A.tx + slack, vt = A.ty - (float)y0 * sy + slack, vb = A.ty - (float)y1 * sy - slack;
+  const int ntri = A.ntri;
+  int m = 0;
+  for (int base = 0; base < ntri; base += 64) {
+    const int f = base + lane;
+    bool keep = false;
+    if (f < ntri) {
+      const int4 T = A.tris[f];
+      const v3 a = ld3(X + 3 * T.x) - eye, b = ld3(X + 3 * T.y) - eye, c = ld3(X + 3 * T.z) - eye;
+      const float za = dot(a, fwd), zb = dot(b, fwd), zc = dot(c, fwd);
+      const float zmin = fminf(za, fminf(zb, zc)), zmax = fmaxf(za, fmaxf(zb, zc));
+      if (zmax >= 0.99f * near && zmin <= 1.01f * far) {      // a hit's depth lies between the vertices' depths
+        if (zmin < near) keep = true;      // a vertex before the near plane or behind the eye: not projected
+        else {
+          const float ia = 1.f / za, ib = 1.f / zb, ic = 1.f / zc;
+          const float xa = dot(a, right) * ia, xb = dot(b, right) * ib, xc = dot(c, right) * ic;
+          const float ya = dot(a, up) * ia, yb = dot(b, up) * ib, yc = dot(c, up) * ic;
+          keep = !(fmaxf(xa, fmaxf(xb, xc)) < ul || fminf(xa, fminf(xb, xc)) > ur || fmaxf(ya, fmaxf(yb, yc)) < vb || fminf(ya, fminf(yb, yc)) > vt);
+        }
+      }
+    }
+    const uint64_t mask = wave_ballot(keep);
+    if (keep) list[m + wave_rank(mask)] = f;
+    m += popc64(mask);
+    if (m + 64 <= AGX_RENDER_LIST && base + 64 < ntri) continue;
+    wave_sync();
+    for (int k = 0; k < m; k++) {
+      const int fi = wave_uniform(list[k]);
+      const int4 T = A.tris[fi];
+      const v3 a = ld3(X + 3 * T.x), e1 = ld3(X + 3 * T.y) - a, e2 = ld3(X + 3 * T.z) - a;      // wave uniform: scalar loads
+      // from the eye: tv = eye - a, det = e1 . (d x e2), u = tv . (d x e2) / det, v = d . (tv x e1) / det, t = e2 . (tv x e1) / det
+      const v3 tv = eye - a, nrm = cross(e1, e2), q = cross(tv, e1), w = cross(e2, tv);
+      const float det = -dot(dw, nrm), inv = __builtin_amdgcn_rcpf(det);
+      const float u = dot(dw, w) * inv, v = dot(dw, q) * inv, t = dot(e2, q) * inv;
+      if (det != 0.f && u >= 0.f && v >= 0.f && u + v <= 1.f && t >= near && t <= far && t < best_t) {      // false for every NaN
+        const float s = (det > 0.f ? 1.f : -1.f) * wave_rsqrt(dot(nrm, nrm));      // the unit normal on the side of the eye: n . d < 0
+        best_t = t; best = fi; best_n = s * nrm;
+      }
+    }
+    wave_sync();      // before the next round writes the list
+    m = 0;
+  }
+  if (!inside || best < 0) return;
+  A.depth[pix] = best_t;
+  A.seg[pix] = ncoll + best;
+  if (A.rgba) {
+    const float shade = A.ambient + A.diffuse * fmaxf(0.f, best_n.x * A.light[0] + best_n.y * A.light[1] + best_n.z * A.light[2]);
+    const float* col = A.colours + 3 * AGX_COLOUR_GARMENT;
+    const uint32_t r = (uint32_t)rintf(255.f * fminf(1.f, col[0] * shade)), g = (uint32_t)rintf(255.f * fminf(1.f, col[1] * shade)),
+                   b = (uint32_t)rintf(255.f * fminf(1.f, col[2] * shade));
+    A.rgba[pix] = r | g << 8 | b << 16 | 255u << 24;
+  }
+}
+
+void agx_launch_render(hipStream_t st, const agx_render_args& A, int count, bool garment) {
   const int tiles = ((A.width + AGX_RENDER_TW - 1) / AGX_RENDER_TW) * ((A.height + AGX_RENDER_TH - 1) / AGX_RENDER_TH);
   hipLaunchKernelGGL(agx_render_kernel, dim3(tiles, count), dim3(64), 0, st, A);
+  if (garment) hipLaunchKernelGGL(agx_render_garment_kernel, dim3(tiles, count), dim3(64), 0, st, A);
 }

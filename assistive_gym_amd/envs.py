@@ -255,15 +255,16 @@ class AssistiveEnv(_Base):
     def render(self, mode='human'):
         return None          # GUI / EGL rendering is outside the hot path
 
-    def setup_camera(self, camera_eye=(0.5, -0.75, 1.5), camera_target=(-0.2, 0, 0.75), fov=60, camera_width=1920 // 4, camera_height=1080 // 4):
-        """env.py:342-346.  The camera is the batched one (assistive_gym_amd/camera.py) on this environment's stepper: it draws the collision geometry"""
-        self.camera_width, self.camera_height = camera_width, camera_height
+    def setup_camera(self, camera_eye=(0.5, -0.75, 1.5), camera_target=(-0.2, 0, 0.75), fov=60, camera_width=1920 // 4, camera_height=1080 // 4, garment=False):
+        """env.py:342-346.  The camera is the batched one (assistive_gym_amd/camera.py) on this environment's stepper: it draws the collision geometry
+        and, with garment=True in a Dressing* environment, the gown"""
+        self.camera_width, self.camera_height, self._camera_garment = camera_width, camera_height, bool(garment)
         self.view_matrix, self.projection_matrix = ('eye', tuple(camera_eye), tuple(camera_target)), fov
         self._camera = None
 
-    def setup_camera_rpy(self, camera_target=(-0.2, 0, 0.75), distance=1.5, rpy=(0, -35, 40), fov=60, camera_width=1920 // 4, camera_height=1080 // 4):
-        """env.py:348-352: rpy = (roll, pitch, yaw) in degrees, the z axis up"""
-        self.camera_width, self.camera_height = camera_width, camera_height
+    def setup_camera_rpy(self, camera_target=(-0.2, 0, 0.75), distance=1.5, rpy=(0, -35, 40), fov=60, camera_width=1920 // 4, camera_height=1080 // 4, garment=False):
+        """env.py:348-352: rpy = (roll, pitch, yaw) in degrees, the z axis up; garment as in setup_camera"""
+        self.camera_width, self.camera_height, self._camera_garment = camera_width, camera_height, bool(garment)
         self.view_matrix, self.projection_matrix = ('rpy', tuple(camera_target), distance, tuple(rpy)), fov
         self._camera = None
 
@@ -278,6 +279,7 @@ class AssistiveEnv(_Base):
                 self._camera.setup_rpy(self.view_matrix[1], self.view_matrix[2], self.view_matrix[3], self.projection_matrix)
             else:
                 self._camera.setup(self.view_matrix[1], self.view_matrix[2], self.projection_matrix)
+            self._camera.set_garment(getattr(self, '_camera_garment', False))
         out = self._camera.render(light_pos=light_pos, ambient=ambient, diffuse=diffuse)
         return out['rgba'][0].cpu().numpy(), bullet_depth(out['depth'][0].cpu().numpy().astype(np.float64)).astype(np.float32)
 

@@ -16,7 +16,8 @@ EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_p
            'agx_observe', 'agx_observe_masked', 'agx_reset_done_at', 'agx_sample_reset', 'agx_reset', 'agx_attach_settle_model', 'agx_reset_done', 'agx_step_host', 'agx_observe_host', 'agx_profile_begin', 'agx_profile_end',
            'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_chunk_count', 'agx_set_env_offset', 'agx_check_collisions',
            'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae', 'agx_ee_arms', 'agx_ee_pose', 'agx_ee_ik',
-           'agx_camera_set', 'agx_render', 'agx_collider_count', 'agx_collider_frames', 'agx_camera_colours']
+           'agx_camera_set', 'agx_render', 'agx_collider_count', 'agx_collider_frames', 'agx_camera_colours',
+           'agx_camera_garment', 'agx_garment_faces', 'agx_camera_garment_colour']
 
 
 class AgxError(RuntimeError):
@@ -43,6 +44,9 @@ def load():
         L.agx_collider_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.agx_collider_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.agx_camera_colours.argtypes = [C.c_void_p]
+        L.agx_camera_garment.argtypes = [C.c_void_p, C.c_int]
+        L.agx_garment_faces.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        L.agx_camera_garment_colour.argtypes = [C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -102,6 +106,13 @@ def camera_colours():
     """agx_camera_colours: the camera's colour table, float32 [12, 3] -- collider tags 0..9 (AGX_TAG_*), the water particles, the background"""
     out = np.zeros((12, 3), dtype=np.float32)
     check(load().agx_camera_colours(out.ctypes.data_as(C.c_void_p)), 'agx_camera_colours')
+    return out
+
+
+def camera_garment_colour():
+    """agx_camera_garment_colour: the colour the camera draws the garment of a dressing scene in, float32 [3] (not a row of camera_colours)"""
+    out = np.zeros(3, dtype=np.float32)
+    check(load().agx_camera_garment_colour(out.ctypes.data_as(C.c_void_p)), 'agx_camera_garment_colour')
     return out
 
 
@@ -294,6 +305,20 @@ class Stepper:
         l = np.ascontiguousarray(light, dtype=np.float32).reshape(3)
         check(self.L.agx_render(self.h, int(env0), int(count), l.ctypes.data, float(ambient), float(diffuse), depth.data_ptr() if depth is not None else None,
                                 seg.data_ptr() if seg is not None else None, rgba.data_ptr() if rgba is not None else None, stream or None), 'agx_render')
+
+    def camera_garment(self, on=True):
+        """agx_camera_garment: draw the garment of a dressing scene in the images of render (off by default); after camera_set"""
+        check(self.L.agx_camera_garment(self.h, int(bool(on))), 'agx_camera_garment')
+
+    def garment_faces(self):
+        """agx_garment_faces: the garment's triangle table, int32 [faces, 3] node indices; face f is the segmentation value collider_count() + f.
+        [0, 3] for a model without a garment"""
+        n = C.c_int()
+        check(self.L.agx_garment_faces(self.h, C.byref(n), None), 'agx_garment_faces')
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            check(self.L.agx_garment_faces(self.h, C.byref(n), out.ctypes.data_as(C.c_void_p)), 'agx_garment_faces')
+        return out
 
     def settle(self, n_substeps, stream=0):
         check(self.L.agx_settle(self.h, C.c_int(n_substeps), C.c_void_p(stream)), 'agx_settle')

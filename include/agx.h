@@ -237,8 +237,8 @@ int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int fram
  * of the model blob: every collider by its vertex count -- 1 a sphere, 2 a capsule, 3 and more the convex polytope of the vertices with each face
  * plane pushed outward by AGX_C_RADIUS (a flat or degenerate vertex set: its bounding box) -- for the environment's gender only, where the
  * collide phase places it (a food or water particle the task has retired sits beyond the far plane), and the water particles of a drinking scene as
- * spheres of the section's MARGIN.  The garment of a dressing scene is NOT drawn.  Not Bullet's rasteriser: no visual meshes, no textures,
- * no shadows, no specular term.
+ * spheres of the section's MARGIN.  The garment of a dressing scene is drawn once agx_camera_garment switches it on (below; off by default).
+ * Not Bullet's rasteriser: no visual meshes, no textures, no shadows, no specular term.
  * Pixel (i, j), row 0 at the top, casts one ray through its centre: in camera space ((2 (i + 0.5) / w - 1) aspect tan(fov / 2),
  * (1 - 2 (j + 0.5) / h) tan(fov / 2), -1), not normalised, so the ray parameter t is the view-space depth.  A convex collider meets the ray in an
  * interval; its hit is where the ray enters, or where it leaves if it enters before the near plane.  The nearest hit with near <= t <= far wins,
@@ -249,7 +249,7 @@ int agx_ee_ik(agx_handle h, const float* target_dev, int target_stride, int fram
  * frame table; later calls only move the camera.
  * agx_render: environments [env0, env0 + count), count <= 65535, into [count][height][width] device arrays, each of which may be NULL (not all):
  *   depth_dev float32: t of the hit, `far` where nothing is hit;
- *   seg_dev   int32:   the collider index, ncoll + k for water particle k, -1 for the background;
+ *   seg_dev   int32:   the collider index, ncoll + k for water particle k (ncoll + f for face f of the garment, below), -1 for the background;
  *   rgba_dev  uint8[4] (4-byte aligned): round(255 min(1, colour (ambient + diffuse max(0, n . l)))) per channel, l = light3 normalised (the
  *             direction towards the light), n the outward normal at the hit, colour by the collider's AGX_C_TAG from the table agx_camera_colours
  *             copies out (float[12][3]: tags 0..9, then the water, then the background, which is not shaded); alpha 255.
@@ -264,6 +264,32 @@ int agx_render(agx_handle h, int env0, int count, const float* light3, float amb
 int agx_collider_count(agx_handle h, int* ncoll);
 int agx_collider_frames(agx_handle h, int env0, int count, float* frames_dev, void* stream);
 int agx_camera_colours(float* out36);
+
+/* ---- the garment of a dressing scene in the camera's images (csrc/agx_garment.h, agx_render_garment_kernel of csrc/agx_render.hip: a second
+ * kernel that draws the faces over the images of the rigid caster).  Off by default: with it off agx_render launches what it launches without
+ * these entries and returns the same bits, for every handle; with it on, a pixel no face wins is that same pixel.
+ * Triangle table, from the blob alone: walk the nodes a = 0 .. NN-1 in order and each node's incident-face entries (j, k) (AGX_CL_OFF_FACE, from
+ *   AGX_CL_OFF_NODE) in order; keep (a, j, k) when a < j and a < k.  Every face has three rotated entries, so it is kept exactly once and keeps its
+ *   winding; face f is the f-th kept triple (dressing_baxter: 7,673 faces from 23,019 entries).  A particle section (AGX_CL_PARTICLES, the water)
+ *   has no faces and is not a garment.
+ * Positions: the first [nodes][3] floats of the environment's garment record (agx_cloth_dev) as it stands in stream order when agx_render runs.
+ *   The record is only read.
+ * Hit: the camera's ray eye + t d (d not normalised, t the view-space depth) hits face (a, b, c) when its barycentric coordinates satisfy u >= 0,
+ *   v >= 0, u + v <= 1, the determinant is not 0 and near <= t <= far.  Both sides are visible; a zero-area face is never hit; the garment has no
+ *   thickness (MARGIN is a contact distance and is not drawn).  A face with a node that is not finite is not hit.
+ * Merge with the rigid scene: the smaller t wins; on a tie the lower segmentation value: a collider before a face, a lower face before a higher.
+ * Outputs: seg = ncoll + f (a scene with a garment has no water particles); depth = t; rgba by the camera's formula with n the unit normal of the
+ *   face at its current node positions, signed against the ray (n . d < 0), and the garment's own colour (139, 195, 74) / 256 (the reference's
+ *   gown, dressing.py:153, drawn opaque: alpha 255), which agx_camera_garment_colour copies out (float[3]).
+ * agx_camera_garment: the switch.  AGX_E_ARG for on != 0 on a model without a garment (no cloth section, or a particle section) and for any call
+ *   before agx_camera_set.  The first enabling call builds the triangle table on the host and uploads it; later calls only flip the switch.
+ *   AGX_E_BLOB: the cloth section is malformed (an offset outside the section, a node index >= NN, an entry count that is no multiple of 3).
+ * agx_garment_faces: the table as host_tris[count][3]; host_tris may be NULL to ask for the count only; count = 0 for a model without a garment.
+ *   It needs no camera.
+ * Every check runs before any launch; nothing here writes the state or garment records. */
+int agx_camera_garment(agx_handle h, int on);
+int agx_garment_faces(agx_handle h, int* count, int* host_tris);
+int agx_camera_garment_colour(float* out3);
 
 /* convenience wrappers with HOST buffers (copies included; not the timed path) */
 int agx_step_host(agx_handle h, const float* actions, float* obs, float* reward, uint8_t* done, float* info);
