@@ -88,11 +88,41 @@ static_assert(MAX_COLL <= 512, "collider indices are packed in 9 bits");
 // 163 + 6 = four (profiles/r05/r05x_*)
 constexpr bool LIST_BYTES = MAX_COLL <= 256;
 constexpr int LIST_TAIL = LIST_BYTES ? 8 : 16;
+#ifdef AGX_WL_TEST_CAP   // test-only: a short worklist, so that ordinary substeps go through the flush between groups, the batches of A colliders and the overflow (tests/test_emu_collide_front.py)
+constexpr int WL_CAP = AGX_WL_TEST_CAP;
+static_assert(WL_CAP >= 1 && WL_CAP <= WL_MAX - LIST_TAIL, "AGX_WL_TEST_CAP only lowers the cap");
+#else
 constexpr int WL_CAP = WL_MAX - LIST_TAIL;
+static_assert(WL_CAP >= 128, "a flush of at least two full passes");
+static_assert(!(TASK == AGX_TASK_FEEDING && MAX_COLL == 256 && ARENA_WORDS == 3592) || WL_CAP == 174, "the feeding variant: 174 entries make three narrowphase passes instead of four");
+#endif
 template <bool B> struct ListIndex { typedef unsigned short type; };
 template <> struct ListIndex<true> { typedef uint8_t type; };
 typedef ListIndex<LIST_BYTES>::type list_t;
-static_assert(WL_CAP >= 128, "a flush of at least two full passes");
+// AGX_COLLIDE_FRONT.  The group cull and the contact selection around the narrowphase decide WHICH groups are swept and WHICH candidate takes which
+// contact slot; no floating-point expression of theirs reaches a result except through fminf / fmaxf (exact, order-free) and comparisons.
+// 1 (the DEFAULT):
+//   * cull: lane l first reduces a block of 2^k consecutive colliders (64 blocks cover the table) to one box in the candidate area (dead until the
+//     first flush); lane g then builds the union box of each of its two ranges from the few head and tail colliders and the whole blocks in
+//     between -- about 40 steps for the 134-collider range of the feeding scene instead of 134;
+//   * selection: every worklist entry finds its own (group, A collider) segment from ballots of the segment starts, ranks itself among the
+//     entries of that segment by (gap, index) and takes slot = contacts before the flush + selected entries of earlier segments + rank -- two
+//     rounds of ballots for the whole list instead of a wave_min + ballot round per kept contact of every segment.
+// 0: one lane walks each range collider by collider, and the selection takes one segment at a time, as before this switch existed
+//    (lib/variants/frontplain.so; tests/test_gpu_collide_front.py and tests/test_emu_collide_front.py compare the bits).
+#ifndef AGX_COLLIDE_FRONT
+#define AGX_COLLIDE_FRONT 1
+#endif
+#if AGX_COLLIDE_FRONT < 0 || AGX_COLLIDE_FRONT > 1
+#error "AGX_COLLIDE_FRONT: 0 or 1"
+#endif
+// the two parts on their own, for same-box A/B runs (profiles/collide_front/)
+#ifndef AGX_FRONT_CULL
+#define AGX_FRONT_CULL AGX_COLLIDE_FRONT
+#endif
+#ifndef AGX_FRONT_SELECT
+#define AGX_FRONT_SELECT AGX_COLLIDE_FRONT
+#endif
 
 AGX_DEV void emit_from_cand(Ctx& c, int slot, int idx) {
   const float* L = c.lds; const int pr = c.ldsi[L_ARENA + A_WL + idx]; const float* cd = L + L_ARENA + A_CAND + CAND_STRIDE * idx;
@@ -425,12 +455,60 @@ AGX_DEV void collide_flush(Ctx& c, int wn, CollideState& cs, float brk, float sl
   (void)any_manifold_query;
   wave_sync();
   if (c.timing) { long long t = wave_clock(); c.tm[11] += t - ct0; ct0 = t; }
-  // 4. selection, one (group, A collider) segment at a time.  The loop only decides which candidate
+  // 4. selection per (group, A collider) segment: in one pass over the whole list (AGX_COLLIDE_FRONT), or one segment at a time in the loop
+  // below (-DAGX_COLLIDE_FRONT=0, and any flush with a run of more than 128 entries).  Either only decides which candidate
   // becomes which contact slot (SEL[]); the contact records are then written by one lane per contact, so
   // that their blob reads (bodies, friction) overlap instead of queueing up behind each other.
   int* SEL = c.ldsi + L_ARENA + A_CAND + CAND_STRIDE * WL_CAP;      // the sweep's lists are dead by now
   const int ncon0 = cs.ncon;
   int cur = 0;
+#if AGX_FRONT_SELECT
+  // one pass (AGX_COLLIDE_FRONT above): lane l holds the entries l, l + 64, ...; a segment is a run of entries with the same key
+  constexpr int SEL_R = (WL_CAP + 63) / 64;
+  uint64_t SB[SEL_R], QB[SEL_R];      // segment starts, selected entries
+#pragma unroll
+  for (int r = 0; r < SEL_R; r++) {
+    const int i = 64 * r + lane;
+    SB[r] = wave_ballot(i < wn && (i == 0 || ((WL[i > 0 ? i - 1 : 0] ^ WL[i < wn ? i : 0]) & WL_KEY_MASK) != 0));
+  }
+  int total = 0, seg0[SEL_R], rank[SEL_R]; bool longrun = false;
+#pragma unroll
+  for (int r = 0; r < SEL_R; r++) {
+    const int i = 64 * r + lane; const bool has = i < wn;
+    int s = 0, e = wn;      // the last start at or before the entry, the first one behind it
+#pragma unroll
+    for (int q = 0; q <= r; q++) { const uint64_t m = q < r ? SB[q] : SB[q] & (~0ull >> (63 - lane)); if (m) s = 64 * q + 63 - clz64(m); }
+#pragma unroll
+    for (int q = SEL_R - 1; q >= r; q--) { const uint64_t m = q > r ? SB[q] : (lane < 63 ? SB[q] & (~0ull << (lane + 1)) : 0ull); if (m) e = 64 * q + ffs64(m); }
+    longrun = longrun || (has && e - s > 128);
+    const float gi = has ? CD[CAND_STRIDE * i] : 3.0e38f;
+    const int keep = wave_shfl_i(G.keep, has ? (WL[i] >> 18) & 63 : 0);
+    int rk = 0;
+    if (gi < 1.0e38f) {
+      if (keep == 0) { for (int j = s; j < i; j++) rk += CD[CAND_STRIDE * j] < 1.0e38f ? 1 : 0; }      // everything, in enumeration order
+      else for (int j = s; j < e; j++) { const float gj = CD[CAND_STRIDE * j]; rk += (gj < gi || (gj == gi && j < i)) ? 1 : 0; }   // equal gaps: the lower index first
+    }
+    seg0[r] = s; rank[r] = rk;
+    QB[r] = wave_ballot(gi < 1.0e38f && (keep == 0 || rk < keep));
+    total += popc64(QB[r]);
+  }
+  // a run of more than 128 entries is cut there and its remainder selected on its own: left to the loop below, with everything else of this flush
+  if (!wave_any(longrun)) {
+#pragma unroll
+    for (int r = 0; r < SEL_R; r++) {
+      if (!(QB[r] >> lane & 1)) continue;
+      int before = 0;      // selected entries of the earlier segments
+#pragma unroll
+      for (int q = 0; q <= r; q++) { const int d = seg0[r] - 64 * q; before += d <= 0 ? 0 : popc64(d >= 64 ? QB[q] : QB[q] & ((1ull << d) - 1ull)); }
+      const int slot = ncon0 + before + rank[r];
+      if (slot < cs.maxc) SEL[slot - ncon0] = 64 * r + lane;
+    }
+    int room = cs.maxc - cs.ncon; if (room < 0) room = 0;
+    if (total > room) { cs.overflow += total - room; total = room; }
+    cs.ncon += total;
+    cur = wn;
+  }
+#endif
   while (cur < wn) {
     const int key = WL[cur] & WL_KEY_MASK;            // group and A collider
     const int g = (key >> 18) & 63, keep = wave_bcast_i(G.keep, g);
@@ -525,6 +603,20 @@ AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gfl
   return wn;
 }
 
+#if AGX_FRONT_CULL
+// union box of the colliders [r0, r1) (into lo / hi, which hold the identity or an earlier union): the colliders up to the first block boundary,
+// the whole blocks in between (their boxes at AB[A_CAND], 2^bsh colliders each), the colliders behind the last boundary.  fminf / fmaxf in
+// another order than one collider after the other: the same floats.
+AGX_DEV void range_box(const float* AB, int bsh, int r0, int r1, float* lo, float* hi) {
+  int bl0 = (r0 + (1 << bsh) - 1) >> bsh, bl1 = r1 >> bsh;
+  int h1 = bl0 << bsh, t0 = bl1 << bsh;
+  if (bl0 >= bl1) { h1 = r1; t0 = r1; bl1 = bl0; }      // no whole block inside
+  for (int i = r0; i < h1; i++) for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], AB[ABS * i + k]); hi[k] = fmaxf(hi[k], AB[ABS * i + 3 + k]); }
+  for (int b = bl0; b < bl1; b++) for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], AB[A_CAND + 6 * b + k]); hi[k] = fmaxf(hi[k], AB[A_CAND + 6 * b + 3 + k]); }
+  for (int i = t0; i < r1; i++) for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], AB[ABS * i + k]); hi[k] = fmaxf(hi[k], AB[ABS * i + 3 + k]); }
+}
+#endif
+
 AGX_DEV void collide(Ctx& c) {
   float* L = c.lds; float* AB = L + L_ARENA; const int lane = c.lane;
   const float brk = PRM(c, AGX_P_CONTACT_BREAK), slack = PRM(c, AGX_P_CONTACT_SLACK);
@@ -564,7 +656,18 @@ AGX_DEV void collide(Ctx& c) {
   wave_sync();
   AGX_CTICK(8)
   const int gender = c.ldsi[L_ST + c.s_env + AGX_E_GENDER];
-  // body-level cull of every group at once: lane g scans both collider ranges of group g
+#if AGX_FRONT_CULL
+  // the boxes of 64 blocks of 2^bsh consecutive colliders, lane l = block l (AGX_COLLIDE_FRONT above)
+  int bsh = 0; while ((64 << bsh) < c.ncoll) bsh++;
+  {
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    const int i0 = lane << bsh, i1 = i0 + (1 << bsh) < c.ncoll ? i0 + (1 << bsh) : c.ncoll;
+    for (int i = i0; i < i1; i++) for (int k = 0; k < 3; k++) { lo[k] = fminf(lo[k], AB[ABS * i + k]); hi[k] = fmaxf(hi[k], AB[ABS * i + 3 + k]); }
+    for (int k = 0; k < 3; k++) { AB[A_CAND + 6 * lane + k] = lo[k]; AB[A_CAND + 6 * lane + 3 + k] = hi[k]; }
+  }
+  wave_sync();
+#endif
+  // body-level cull of every group at once: lane g builds the union boxes of both collider ranges of group g
   uint64_t live_groups = 0;
   GroupRegs G; G.a0 = 0; G.a1 = 0; G.b0 = 0; G.b1 = 0; G.flags = 0; G.keep = 0;
   for (int k = 0; k < 3; k++) { G.alo[k] = 0.f; G.ahi[k] = 0.f; G.blo[k] = 0.f; G.bhi[k] = 0.f; }
@@ -581,8 +684,12 @@ AGX_DEV void collide(Ctx& c) {
                           !((G.flags & 32) && c.nrobot + c.nhdof <= 32 && ((~c.frozen >> c.nrobot) & ((1u << c.nhdof) - 1u)) == 0);
       if (a1 > a0 && b1 > b0 && wanted) {
         float alo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, ahi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, blo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, bhi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+#if AGX_FRONT_CULL
+        range_box(AB, bsh, a0, a1, alo, ahi); range_box(AB, bsh, b0, b1, blo, bhi);
+#else
         for (int i = a0; i < a1; i++) for (int k = 0; k < 3; k++) { alo[k] = fminf(alo[k], AB[ABS * i + k]); ahi[k] = fmaxf(ahi[k], AB[ABS * i + 3 + k]); }
         for (int i = b0; i < b1; i++) for (int k = 0; k < 3; k++) { blo[k] = fminf(blo[k], AB[ABS * i + k]); bhi[k] = fmaxf(bhi[k], AB[ABS * i + 3 + k]); }
+#endif
         live = true;
         for (int k = 0; k < 3; k++) if (alo[k] > bhi[k] + mg || blo[k] > ahi[k] + mg) live = false;
         for (int k = 0; k < 3; k++) { G.alo[k] = alo[k]; G.ahi[k] = ahi[k]; G.blo[k] = blo[k]; G.bhi[k] = bhi[k]; }
