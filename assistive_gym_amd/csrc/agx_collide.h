@@ -108,7 +108,15 @@ typedef ListIndex<LIST_BYTES>::type list_t;
 //   * selection: every worklist entry finds its own (group, A collider) segment from ballots of the segment starts, ranks itself among the
 //     entries of that segment by (gap, index) and takes slot = contacts before the flush + selected entries of earlier segments + rank -- two
 //     rounds of ballots for the whole list instead of a wave_min + ballot round per kept contact of every segment.
-// 0: one lane walks each range collider by collider, and the selection takes one segment at a time, as before this switch existed
+//   * sweep: a WINDOW of consecutive live groups is swept at once (collide_sweep_window below).  Level 1 takes the collider ranges of all its
+//     groups, concatenated, 64 per round, and packs the surviving colliders of every (group, side) into the list area one list behind the other;
+//     the window ends in front of the first group whose lists no longer fit there.  Level 2 runs ONE pair grid over the concatenated pair counts:
+//     a lane finds its group from the prefix sums, then (a, b, face point) inside it, and survivors are appended by ballot rank -- group-major
+//     concatenation plus ballot rank is the enumeration order of the serial sweep.  The grid queues what passes the box test and runs the tests
+//     that read the blob 64 queued pairs at a time (half as many rounds of load chains as grid rounds in the feeding scene).  The grid counts survivors per group, so the first group that
+//     does not fit behind the pending entries is found and the units are flushed exactly where the serial loop flushes them.
+// 0: one lane walks each range collider by collider, the selection takes one segment at a time and every live group is swept on its own (two
+//    levels, a load chain per group), as before this switch existed
 //    (lib/variants/frontplain.so; tests/test_gpu_collide_front.py and tests/test_emu_collide_front.py compare the bits).
 #ifndef AGX_COLLIDE_FRONT
 #define AGX_COLLIDE_FRONT 1
@@ -122,6 +130,24 @@ typedef ListIndex<LIST_BYTES>::type list_t;
 #endif
 #ifndef AGX_FRONT_SELECT
 #define AGX_FRONT_SELECT AGX_COLLIDE_FRONT
+#endif
+#ifndef AGX_FRONT_SWEEP      // (lib/variants/sweepserial.so: the windowed sweep alone switched off; tests/test_gpu_collide_sweep.py, tests/test_emu_collide_sweep.py)
+#define AGX_FRONT_SWEEP AGX_COLLIDE_FRONT
+#endif
+// the list area behind the worklist holds 256 collider indices (bytes in 8 candidate entries, or 16-bit words in 16)
+constexpr int LIST_N = 256;
+static_assert(LIST_N * (int)sizeof(list_t) == LIST_TAIL * CAND_STRIDE * 4, "the two collider lists fill the tail of the candidate area");
+#ifdef AGX_SWEEP_TEST_LIST   // test-only: a short list area, so that ordinary substeps cut their windows by list space (tests/test_emu_collide_sweep.py)
+constexpr int LIST_CAP = AGX_SWEEP_TEST_LIST;
+static_assert(LIST_CAP >= 2 && LIST_CAP <= LIST_N, "AGX_SWEEP_TEST_LIST only lowers the capacity");
+#else
+constexpr int LIST_CAP = LIST_N;
+#endif
+#ifdef AGX_SWEEP_TEST_WINDOW   // test-only: at most this many groups per window
+constexpr int SWEEP_WINDOW = AGX_SWEEP_TEST_WINDOW;
+static_assert(SWEEP_WINDOW >= 1 && SWEEP_WINDOW <= 64, "AGX_SWEEP_TEST_WINDOW: 1 to 64 groups");
+#else
+constexpr int SWEEP_WINDOW = 64;
 #endif
 
 AGX_DEV void emit_from_cand(Ctx& c, int slot, int idx) {
@@ -549,9 +575,11 @@ AGX_DEV void collide_flush(Ctx& c, int wn, CollideState& cs, float brk, float sl
   if (c.timing) { long long t = wave_clock(); c.tm[12] += t - ct0; }
 }
 
+struct SweepStat { int windows, rounds1, rounds2, rounds3; };      // debug path: sweeps (windows) of a substep, their level-1 and level-2 rounds, and the level-2 rounds that ran level 3
+#if !AGX_FRONT_SWEEP
 // broadphase sweep of A colliders [aa, ab) x B range of group g, appended to the worklist at wn.
 // returns the new count (may exceed WL_MAX: entries beyond it are not stored)
-AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gflags, float mg, int wn, int rep, const GroupRegs& G) {
+AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gflags, float mg, int wn, int rep, const GroupRegs& G, SweepStat& stat) {
   const float* AB = c.lds + L_ARENA; int* WL = c.ldsi + L_ARENA + A_WL; const int lane = c.lane;
   const bool same = gflags & 1, no_adjacent = gflags & 4;   // bit2, self-collision: not the same link, not parent and child
   // level 1: the A colliders whose box reaches the union box of the B range and vice versa (the union
@@ -570,8 +598,10 @@ AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gfl
       const uint64_t m = wave_ballot(ok);
       if (ok) LIST[128 * side + nlive[side] + wave_rank(m)] = (list_t)x;
       nlive[side] += popc64(m);
+      stat.rounds1++;
     }
   }
+  stat.windows++;
   const int na_live = nlive[0], nb = nlive[1];
   wave_sync();
   // level 2: the pair grid of the surviving A colliders, in enumeration order
@@ -598,10 +628,159 @@ AGX_DEV int collide_sweep(Ctx& c, int g, int aa, int ab, int b0, int b1, int gfl
     const int slot = wn + wave_rank(m);
     if (ok && slot < WL_CAP) WL[slot] = a | (b << 9) | (g << 18) | (sub << 24);
     wn += popc64(m);
+    stat.rounds2++; stat.rounds3++;
   }
   wave_sync();
   return wn;
 }
+#else
+AGX_DEV uint64_t lanes_below(int e) { return e <= 0 ? 0ull : e >= 64 ? ~0ull : (1ull << e) - 1ull; }      // the lanes 0 .. e - 1
+// the group (bit of `rem`, lane = group) whose half-open interval of positions holds x: the intervals start at `start` (ascending with the group,
+// one behind the other), this round covers the positions [base, base + 64).  Groups that end in front of the round are taken out of rem.
+AGX_DEV int window_group(uint64_t& rem, int start, int base, int x, int l) {
+  for (uint64_t m = rem; m; m &= m - 1) {
+    const int q = ffs64(m), s = wave_bcast_i(start, q);
+    if (s >= base + 64) break;
+    l = x >= s ? q : l; rem = m;
+  }
+  return l;
+}
+// what a sweep of a window accepted: nacc of its groups fit behind the pending entries and end the worklist at wn; over: the group `gnext` behind
+// them did not fit (otherwise gnext is the first group behind the window); end0: where the window's first group alone ends the list (not capped)
+struct SweepOut { int nacc, wn, end0, gnext; bool over; };
+// Broadphase sweep of a window of live groups, appended to the worklist at wn0 (AGX_COLLIDE_FRONT above).  The window: the live groups from g0 on,
+// at most maxg of them, as far as their level-1 lists fit the list area; of g0 the A colliders [aa, ab) only (a batch of a split group comes with
+// maxg = 1).  Lane = group throughout: the group's parameters and boxes are G's, its list offsets, counts and prefix sums live beside them.
+AGX_DEV void collide_sweep_window(Ctx& c, int g0, int aa, int ab, int maxg, uint64_t live_groups, int wn0, float brk, float slack, const GroupRegs& G,
+                                  CollideState& cs, SweepOut& o, SweepStat& stat) {
+  const float* AB = c.lds + L_ARENA; int* WL = c.ldsi + L_ARENA + A_WL; const int lane = c.lane;
+  list_t* LIST = (list_t*)(c.ldsi + L_ARENA + A_CAND + CAND_STRIDE * WL_CAP);   // LIST_CAP indices: the A list, then the B list, of one group after the other
+  uint64_t cand = live_groups & (~0ull << g0);
+  if (maxg < 64) { uint64_t t = cand; cand = 0; for (int k = 0; k < maxg && t; k++) { cand |= t & (~t + 1ull); t &= t - 1; } }
+  const bool in = cand >> lane & 1;
+  const int ra0 = lane == g0 ? aa : G.a0, lenA = in ? (lane == g0 ? ab : G.a1) - ra0 : 0, lenB = in ? G.b1 - G.b0 : 0;
+  const int mgbit = (G.flags & (2 | 64)) ? 1 : 0;      // the group's margin: brk (bit1: existence query; bit6: every contact inside the break distance), or slack
+  // level 1: the colliders whose box reaches the union box of the opposite range (computed by the group cull, lane g holds them), in ascending
+  // order.  Position x of the concatenated ranges (A range, then B range, group after group) is one collider of one (group, side).
+  int S = 0, T = 0;
+  for (uint64_t m = cand; m; m &= m - 1) { const int q = ffs64(m), v = wave_bcast_i(lenA + lenB, q); if (lane == q) S = T; T += v; }
+  const int pk1 = ra0 | (G.b0 << 9) | (lenA << 18) | (mgbit << 28);
+  int cA = 0, cB = 0, cE = 0;      // list entries in front of this group's A list, its B list, and behind both
+  {
+    uint64_t rem = cand; int run = 0;
+    for (int base = 0; base < T; base += 64) {
+      const int x = base + lane;
+      const int l = window_group(rem, S, base, x, g0);
+      const int pk = wave_shfl_i(pk1, l), xs = x - wave_shfl_i(S, l);
+      const bool sideB = xs >= ((pk >> 18) & 1023);
+      const int col = sideB ? ((pk >> 9) & 511) + xs - ((pk >> 18) & 1023) : (pk & 511) + xs;
+      const float mg = (pk >> 28 & 1) ? brk : slack;
+      bool ok = x < T;
+      for (int q = 0; q < 3; q++) {
+        const float alo = wave_shfl(G.alo[q], l), ahi = wave_shfl(G.ahi[q], l), blo = wave_shfl(G.blo[q], l), bhi = wave_shfl(G.bhi[q], l);
+        const float ulo = sideB ? alo : blo, uhi = sideB ? ahi : bhi;
+        if (ok && (AB[ABS * col + q] > uhi + mg || ulo > AB[ABS * col + 3 + q] + mg)) ok = false;
+      }
+      const uint64_t m = wave_ballot(ok);
+      const int slot = run + wave_rank(m);
+      if (ok && slot < LIST_CAP) LIST[slot] = (list_t)col;
+      cA += popc64(m & lanes_below(S - base)); cB += popc64(m & lanes_below(S + lenA - base)); cE += popc64(m & lanes_below(S + lenA + lenB - base));
+      run += popc64(m);
+      stat.rounds1++;
+    }
+  }
+  // the window ends in front of the first group whose lists do not fit behind the earlier ones
+  const uint64_t nofit = wave_ballot(in && cE > LIST_CAP);
+  uint64_t win = nofit ? cand & lanes_below(ffs64(nofit)) : cand;
+  if (!win) {      // lists longer than the whole area: the group is swept with what fits of them, the rest is counted as overflow
+    win = 1ull << g0; cs.overflow += wave_bcast_i(cE, g0) - LIST_CAP;
+    cB = cB < LIST_CAP ? cB : LIST_CAP; cE = LIST_CAP;
+  }
+  const bool w = win >> lane & 1;
+  const int nA = cB - cA, nB = cE - cB;
+  wave_sync();
+  // level 2: one pair grid over the pair counts of the window's groups, one behind the other, in enumeration order (groups against static world
+  // boxes: every pair is enumerated rep = 1 + AGX_FACE_EXTRA times, entry `sub` > 0 standing for the sub-th extra point of the face manifold)
+  const bool face = w && face_box(c, G.b0);      // B ranges are homogeneous (table boxes, the ground plane, ...)
+  const int np = w ? nA * nB * (face ? 1 + AGX_FACE_EXTRA : 1) : 0;
+  int P = 0, NP = 0;
+  for (uint64_t m = win; m; m &= m - 1) { const int q = ffs64(m), v = wave_bcast_i(np, q); if (lane == q) P = NP; NP += v; }
+  const int pk2 = cA | (cB << 9) | (nB << 18) | ((face ? 1 : 0) << 27) | ((G.flags & 1) << 28) | ((G.flags & 4) << 27) | (mgbit << 30);
+  const int pend0 = wave_bcast_i(np, g0);
+  // The grid runs in two stages.  Stage A, 64 grid points per round, needs the lists and the LDS box table only: the point's group and pair, the
+  // `same` rule and the box test with the group's margin; what passes is queued as a worklist word, in order.  Stage B, whenever 64 pairs are
+  // queued (and for the rest at the end), runs the tests that read the blob -- the face-point rule for sub > 0, no_adjacent, rel_travel and the two
+  // sphere_box_apart -- so that their load chains are paid per 64 box-test survivors and not per 64 grid points.  A conjunction of the same
+  // tests in another order, and the queue keeps the order: the same survivors in the same order.
+  int* Q = c.ldsi + L_ARENA + A_CAND;      // ring of 128 queued pairs at the head of the candidate area (dead until the flush; the lists are in its tail)
+  constexpr int QM = 127;
+  static_assert(CAND_STRIDE * WL_CAP >= QM + 1, "the queue of the sweep lies in front of the lists");
+  int E = 0, wn = wn0;      // survivors up to the end of this group; of the whole window
+  int Aq = 0, qh = 0, qn = 0, popped = 0;      // pairs queued up to the end of this group; head and length of the queue, pairs taken from it
+  uint64_t rem = wave_ballot(np > 0);
+  for (int base = 0;; base += 64) {
+    const bool more = base < NP;
+    if (more) {
+      const int p = base + lane; bool ok = p < NP;
+      const int l = window_group(rem, P, base, p, g0);
+      const int pk = wave_shfl_i(pk2, l), ps = wave_shfl_i(P, l), lp = ok ? p - ps : 0;
+      const bool rep = pk >> 27 & 1, same = pk >> 28 & 1;
+      const float mg = (pk >> 30 & 1) ? brk : slack;
+      const int pq = rep ? lp / (1 + AGX_FACE_EXTRA) : lp, sub = rep ? lp - pq * (1 + AGX_FACE_EXTRA) : 0;
+      const int nb = ok ? (pk >> 18) & 511 : 1;
+      int ai = (int)((float)pq / (float)nb), bi = pq - ai * nb;      // pq < 2^16: the quotient is off by one at most
+      if (bi < 0) { ai--; bi += nb; } else if (bi >= nb) { ai++; bi -= nb; }
+      const int a = ok ? LIST[(pk & 511) + ai] : 0, b = ok ? LIST[((pk >> 9) & 511) + bi] : 0;
+      ok = ok && (!same || b > a);
+      if (ok) for (int q = 0; q < 3; q++) if (AB[ABS * a + q] > AB[ABS * b + 3 + q] + mg || AB[ABS * b + q] > AB[ABS * a + 3 + q] + mg) ok = false;
+      const uint64_t m = wave_ballot(ok);
+      if (ok) Q[(qh + qn + wave_rank(m)) & QM] = a | (b << 9) | (l << 18) | (sub << 24);
+      Aq += popc64(m & lanes_below(P + np - base));
+      qn += popc64(m);
+      stat.rounds2++;
+    }
+    if (!more && qn == 0) break;
+    if (more && qn < 64) continue;
+    wave_sync();
+    const int n = qn < 64 ? qn : 64;
+    bool ok = lane < n;
+    const int e = ok ? Q[(qh + lane) & QM] : 0;
+    const int a = e & 511, b = (e >> 9) & 511, l = (e >> 18) & 63, sub = (e >> 24) & 3;
+    const int pk = wave_shfl_i(pk2, l);
+    const bool no_adjacent = pk >> 29 & 1;   // bit2 of the flags, self-collision: not the same link, not parent and child
+    const float mg = (pk >> 30 & 1) ? brk : slack;
+    ok = ok && (sub == 0 || (face_box(c, b) && CLI(c, a, AGX_C_NVERT) >= 2));
+    if (ok && no_adjacent) {
+      const int la = CLI(c, a, AGX_C_BODY), lb = CLI(c, b, AGX_C_BODY);
+      if (la == lb) ok = false;
+      else if (la >= 0 && la < AGX_BODY_ROBOT_BASE && lb >= 0 && lb < AGX_BODY_ROBOT_BASE && (RBI(c, la, AGX_R_PARENT) == lb || RBI(c, lb, AGX_R_PARENT) == la)) ok = false;
+    }
+    // level 3: bounding sphere of one collider against the body-frame box of the other, both ways
+    // (the second test -- b's bounding sphere against a's body-frame box -- cannot reject what the first one passed when a is a sphere: its
+    // box is the point itself, so the test degenerates to two bounding spheres; skipped then.  Both tests always: 468 k either way, round 4;
+    // profiles/r04/r04q_ab_feeding_one_sided_sphere_cull.txt)
+    if (ok) { const float reach = mg + rel_travel(c, a, b) + 1e-5f; ok = !sphere_box_apart(c, a, b, reach) && (CLI(c, a, AGX_C_NVERT) == 1 || !sphere_box_apart(c, b, a, reach)); }
+    const uint64_t m = wave_ballot(ok);
+    const int slot = wn + wave_rank(m);
+    if (ok && slot < WL_CAP) WL[slot] = e;
+    E += popc64(m & lanes_below(Aq - popped));      // the queue holds the groups in order: its first Aq pairs are those up to the end of this group
+    wn += popc64(m);
+    qh = (qh + n) & QM; qn -= n; popped += n;
+    stat.rounds3++;
+    // the list is full and the first group is complete: the group that does not fit has been seen, and every group in front of it is complete
+    if (wn > WL_CAP && base + 64 >= pend0 && popped >= wave_bcast_i(Aq, g0)) break;
+  }
+  wave_sync();
+  stat.windows++;
+  // the first group whose end lies beyond the worklist is not accepted, nor is any behind it
+  const uint64_t overm = wave_ballot(w && wn0 + E > WL_CAP);
+  const uint64_t acc = overm ? win & lanes_below(ffs64(overm)) : win;
+  o.over = overm != 0ull; o.nacc = popc64(acc);
+  o.gnext = overm ? ffs64(overm) : 64 - clz64(win);
+  o.wn = acc ? wn0 + wave_bcast_i(E, 63 - clz64(acc)) : wn0;
+  o.end0 = wn0 + wave_bcast_i(E, g0);
+}
+#endif
 
 #if AGX_FRONT_CULL
 // union box of the colliders [r0, r1) (into lo / hi, which hold the identity or an earlier union): the colliders up to the first block boundary,
@@ -703,7 +882,10 @@ AGX_DEV void collide(Ctx& c) {
   // entries; then the pending entries are flushed (narrowphase + selection) and the unit is retried
   // on the empty list, split into batches of whole A colliders if it still does not fit.  One sweep
   // and one flush call site keep the kernel's code size down.
+  // (AGX_FRONT_SWEEP: one sweep takes a window of whole groups and accepts those that fit; the first one that does not is the unit that is
+  // retried, so the flushes fall where they fall one group at a time.  A batch of a split group is a window of its own.)
   int wn = 0, g = 0, ab = -1, abatch = 0;
+  SweepStat stat; stat.windows = 0; stat.rounds1 = 0; stat.rounds2 = 0; stat.rounds3 = 0;
   while (true) {
     while (g < c.ngroup && !(live_groups >> g & 1)) g++;
     if (g >= c.ngroup) {
@@ -716,24 +898,35 @@ AGX_DEV void collide(Ctx& c) {
       const int nb = (b1 - b0) * rep;
       if (ab < 0) { ab = a0; abatch = a1 - a0; }
       const int ae = ab + abatch < a1 ? ab + abatch : a1;
-      int wn2 = collide_sweep(c, g, ab, ae, b0, b1, gflags, mg, wn, rep, G);
+#if AGX_FRONT_SWEEP
+      SweepOut so;
+      collide_sweep_window(c, g, ab, ae, (ab > a0 || ae < a1) ? 1 : SWEEP_WINDOW, live_groups, wn, brk, slack, G, cs, so, stat);
+      bool fits = so.nacc > 0, cut = fits && so.over;   // cut: the group behind the accepted ones does not fit behind them
+      int wn2 = fits ? so.wn : so.end0, gnext = so.gnext;
+      (void)gflags; (void)mg;
+#else
+      int wn2 = collide_sweep(c, g, ab, ae, b0, b1, gflags, mg, wn, rep, G, stat);
+      bool fits = wn2 <= WL_CAP, cut = false; int gnext = g + 1;
+#endif
       AGX_CTICK(10)
-      bool fits = wn2 <= WL_CAP;
       if (!fits && wn == 0) {
         const int small = WL_CAP / nb > 0 ? WL_CAP / nb : 1;   // a batch of WL_CAP / nb colliders cannot overflow
         if (abatch > small) { abatch = small; continue; }       // retry this unit in smaller batches
-        cs.overflow += wn2 - WL_CAP; wn2 = WL_CAP; fits = true;  // a single A collider with more than WL_CAP partners
+        cs.overflow += wn2 - WL_CAP; wn2 = WL_CAP; fits = true; gnext = g + 1; cut = false;  // a single A collider with more than WL_CAP partners
       }
       if (fits) {
         wn = wn2; ab = ae;
-        if (ab >= a1) { g++; ab = -1; }
+        if (ab >= a1) { g = gnext; ab = -1; }
         // a unit that was split is flushed batch by batch; whole groups keep accumulating
-        if (ab < 0) continue;
+        if (ab < 0 && !cut) continue;
       }
     }
     collide_flush(c, wn, cs, brk, slack, G); wn = 0;
     ct0 = c.timing ? wave_clock() : 0;
   }
+  // debug: sweeps (windows) of this substep, their level-2 and level-1 rounds, live groups (tools/gpu_build_phases.py, tests/test_emu_collide_sweep.py)
+  if (c.timing) c.tm[15] += stat.rounds3;      // ... and the rounds of the blob-reading tests (level 3)
+  if (c.timing && lane == 0) { c.dbg[DBG_TIME + 20] = (float)stat.windows; c.dbg[DBG_TIME + 21] = (float)stat.rounds2; c.dbg[DBG_TIME + 22] = (float)stat.rounds1; c.dbg[DBG_TIME + 23] = (float)popc64(live_groups); }
   c.ncon = cs.ncon; c.near_mask = cs.near_mask; c.overflow = cs.overflow; c.nqpt = cs.nqpt < MAX_QPT ? cs.nqpt : MAX_QPT;
   wave_sync();
 #undef AGX_CTICK

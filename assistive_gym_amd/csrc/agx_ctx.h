@@ -126,7 +126,7 @@ constexpr int HW_ROWS = MAX_ROWS + 8, HW_DUMMY = MAX_ROWS, HQ_STRIDE = 4, HP_STR
 constexpr int HDR_TABLE_WORDS = MAX_ROWS * (HDR_WIDE ? 16 : 10);
 constexpr int HQ_BASE = HDR_TABLE_WORDS, HP_BASE = HQ_BASE + (HDR_WIDE ? HQ_STRIDE * HW_ROWS : 0), SCR_HDR_WORDS = HP_BASE + (HDR_WIDE ? HP_STRIDE * HW_ROWS : 0);
 constexpr int DBG_CON = 16, DBG_MINV = DBG_CON + MAX_CON * CON_STRIDE, DBG_HDR = DBG_MINV + MAX_DOF * MAX_DOF, DBG_LAM = DBG_HDR + SCR_HDR_WORDS,
-              DBG_TIME = DBG_LAM + MAX_ROWS, DBG_QDD = DBG_TIME + 24,      // (timers: 16 words of the build kernel's phases, 5..7 the solve kernel's; 16..19: steps / rows / scheduled steps / rows per sweep of the wide sweep)
+              DBG_TIME = DBG_LAM + MAX_ROWS, DBG_QDD = DBG_TIME + 24,      // (timers: 16 words of the build kernel's phases, 5..7 the solve kernel's; 16..19: steps / rows / scheduled steps / rows per sweep of the wide sweep; 20..23: sweep windows / level-2 rounds / level-1 rounds / live groups of collide())
               DBG_WORDS = DBG_QDD + MAX_DOF;
 // per-environment scratch record in HBM (L2-resident while its environment is being solved)
 #ifndef AGX_SCR_ENT        // floats of the per-env (J,B) coefficient store: a row keeps one pair per DoF of each articulated block it touches

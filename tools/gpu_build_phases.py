@@ -21,7 +21,11 @@ env.stepper.step_dev(a, env.obs, env.reward, env.done, env.info, torch.cuda.curr
 torch.cuda.synchronize()
 T = dbg.cpu().numpy()[:, lay[6]:lay[6] + 16]
 names = {0: 'kinematics', 1: 'ABA + M^-1', 2: 'predict velocities', 3: 'collide (all)', 4: 'rows', 5: 'PGS', 6: 'integrate + hooks + store', 7: 'row-space set-up (inside PGS)',
-         8: 'collide: AABBs', 9: 'collide: group cull', 10: 'collide: sweep', 11: 'collide: narrowphase (GJK)', 12: 'collide: selection', 13: 'narrowphase pairs', 14: 'narrowphase passes'}
+         8: 'collide: AABBs', 9: 'collide: group cull', 10: 'collide: sweep', 11: 'collide: narrowphase (GJK)', 12: 'collide: selection', 13: 'narrowphase pairs', 14: 'narrowphase passes', 15: 'sweep rounds with blob tests'}
 print(cls, 'contacts %.2f rows %.1f' % (dbg[:, 0].mean().item(), dbg[:, 1].mean().item()))
 for k in sorted(names):
     print('%-32s median %9.0f  mean %9.0f  max %9.0f' % (names[k], np.median(T[:, k]), T[:, k].mean(), T[:, k].max()))
+# counts of the sweep (csrc/agx_collide.h, AGX_FRONT_SWEEP): words 20..23 of the timer block
+S = dbg.cpu().numpy()[:, lay[6] + 20:lay[6] + 24]
+for k, name in enumerate(['sweep windows', 'sweep level-2 rounds', 'sweep level-1 rounds', 'live groups']):
+    print('%-32s median %9.0f  mean %9.2f  max %9.0f' % (name, np.median(S[:, k]), S[:, k].mean(), S[:, k].max()))
