@@ -2,7 +2,7 @@
 
 The kernels are compiled once per variant (limits + task layer: one line of csrc/agx_variants.def, csrc/agx_kernels.hip) and linked with the handle /
 C-ABI code (csrc/agx_api.hip), the policy-step / GAE kernels (csrc/agx_policy.hip), the end-effector IK kernels (csrc/agx_ik.hip) and the camera's
-ray caster (csrc/agx_render.hip)."""
+ray caster (csrc/agx_render.hip) and the closest-point query (csrc/agx_proximity.hip)."""
 import os
 import subprocess
 import sys
@@ -35,7 +35,8 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
     jobs = [(os.path.join(objdir, 'agx_api.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_api.hip')]),
             (os.path.join(objdir, 'agx_policy.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_policy.hip')]),      # policy step + GAE (stateless entries)
             (os.path.join(objdir, 'agx_ik.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_ik.hip')]),              # end-effector pose + IK (agx_ee_pose, agx_ee_ik)
-            (os.path.join(objdir, 'agx_render.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_render.hip')])]      # the camera's ray caster (agx_render)
+            (os.path.join(objdir, 'agx_render.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_render.hip')]),      # the camera's ray caster (agx_render)
+            (os.path.join(objdir, 'agx_proximity.o'), base + list(extra) + ['-c', os.path.join(CSRC, 'agx_proximity.hip')])]      # closest points of collider pairs (agx_proximity)
     reuse = []
     for v in variants.VARIANTS:
         if only and v.name not in only:
@@ -47,6 +48,7 @@ def build(force=False, verbose=False, extra=(), out=None, only=None):
         jobs[1] = (os.path.join(HERE, 'lib', 'obj', 'agx_policy.o'), None)
         jobs[2] = (os.path.join(HERE, 'lib', 'obj', 'agx_ik.o'), None)
         jobs[3] = (os.path.join(HERE, 'lib', 'obj', 'agx_render.o'), None)
+        jobs[4] = (os.path.join(HERE, 'lib', 'obj', 'agx_proximity.o'), None)
     with ThreadPoolExecutor(len(jobs)) as ex:
         list(ex.map(lambda j: j[1] and subprocess.check_call(j[1] + ['-o', j[0]]), jobs))
     subprocess.check_call([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + [j[0] for j in jobs] + reuse)

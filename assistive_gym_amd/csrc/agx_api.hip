@@ -5,6 +5,7 @@
 #include "agx_wave.h"
 #include "agx_variant.h"
 #include "agx_render.h"
+#include "agx_proximity.h"
 #include "agx_hull.h"
 #include "agx_garment.h"
 #include "../../include/agx_blob.h"
@@ -141,6 +142,14 @@ struct agx_camera_s {
   float* lend_depth; int* lend_seg; size_t lend_pixels;      // images the garment kernel merges into where the caller asked for no depth or seg
 };
 
+// the closest-point query of a handle (agx_proximity_set): the pair list and the per-collider flags of csrc/agx_proximity.h, the query's own
+// frame table, all owned, and the arguments every agx_proximity passes
+struct agx_prox_s {
+  agx_prox_args A;
+  float* frames; int* pairs; int* cflags;
+  int ncoll, pairs_cap;
+};
+
 struct agx_handle_s {
   const agx_variant* V;   // the compiled kernel variant serving this model
   // what every launch passes: the model blob, the state / scratch records, their strides (agx_variant.h); with a cloth section (DressingBaxter) the
@@ -173,6 +182,7 @@ struct agx_handle_s {
   agx_handle_s* settle; // bed bathing (AGX_X_FLAGS bit 4): the handle of the rag-doll model whose settled records the sampler reads (agx_attach_settle_model; not owned)
   int settle_substeps;  // substeps of that settle (100 simulation steps: bed_bathing.py:130-131)
   agx_camera_s* cam;    // null until agx_camera_set
+  agx_prox_s* prox;     // null until agx_proximity_set
 };
 
 static void forget_warm(agx_handle_s* h, const uint8_t* mask_dev, hipStream_t st) {
@@ -333,6 +343,7 @@ void agx_destroy(agx_handle h) {
   for (int c = 0; c < 8; c++) for (int k = 0; k < 16; k++) if (h->kev[c][k]) hipEventDestroy(h->kev[c][k]);
   if (h->fork_ev) hipEventDestroy(h->fork_ev);
   for (int k = 0; k < h->n_chunks; k++) { if (h->cs[k]) hipStreamDestroy(h->cs[k]); if (h->join_ev[k]) hipEventDestroy(h->join_ev[k]); }
+  if (h->prox) { hipFree(h->prox->frames); hipFree(h->prox->pairs); hipFree(h->prox->cflags); delete h->prox; }
   delete h;
 }
 
@@ -742,28 +753,41 @@ int agx_collider_frames(agx_handle h, int env0, int count, float* frames_dev, vo
   HIPCHK(hipGetLastError());
   return AGX_OK;
 }
+// the model blob as the device holds it
+static int download_blob(agx_handle h, std::vector<uint32_t>& words) {
+  int32_t hdr[AGX_H_COUNT];
+  HIPCHK(hipMemcpy(hdr, h->L.blob, sizeof hdr, hipMemcpyDeviceToHost));
+  words.resize((size_t)hdr[AGX_H_NWORDS]);
+  HIPCHK(hipMemcpy(words.data(), h->L.blob, words.size() * 4, hipMemcpyDeviceToHost));
+  return AGX_OK;
+}
+// the genders whose environments a collider is part of (bit 0 male, bit 1 female).  A human collider belongs to one gender only where the pair
+// table says so: the B range of a group that has a female alternative is the male human's, the alternative the female's; a group that exists
+// for one gender only (flag bits 3, 4) names that gender's human colliders
+static std::vector<int> collider_genders(const int32_t* bi) {
+  const int ncoll = bi[AGX_H_NCOLL];
+  std::vector<int> genders((size_t)ncoll, 3);
+  for (int g = 0; g < bi[AGX_H_NGROUP]; g++) {
+    const int32_t* G = bi + bi[AGX_H_OFF_GROUP] + g * AGX_G_STRIDE;
+    auto only = [&](int c0, int c1, int bits) { for (int c = c0 < 0 ? 0 : c0; c < c1 && c < ncoll; c++) if (bi[bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE + AGX_C_TAG] == AGX_TAG_HUMAN) genders[c] &= bits; };
+    if (G[AGX_G_B0F] >= 0) { only(G[AGX_G_B0], G[AGX_G_B1], 1); only(G[AGX_G_B0F], G[AGX_G_B1F], 2); }
+    for (int s = 0; s < 2; s++) if (G[AGX_G_FLAGS] & (8 << s)) { only(G[AGX_G_A0], G[AGX_G_A1], 1 << s); only(G[AGX_G_B0], G[AGX_G_B1], 1 << s); }
+  }
+  return genders;
+}
 // the tables of a handle's first camera: per collider the face planes of its hull (none for a sphere or a capsule), the genders that see it and
 // its bounding radius; the frame table
 static int camera_build(agx_handle h) {
-  int32_t hdr[AGX_H_COUNT];
-  HIPCHK(hipMemcpy(hdr, h->L.blob, sizeof hdr, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> words((size_t)hdr[AGX_H_NWORDS]);
-  HIPCHK(hipMemcpy(words.data(), h->L.blob, words.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> words;
+  { const int rc = download_blob(h, words); if (rc) return rc; }
   const int32_t* bi = (const int32_t*)words.data(); const float* bf = (const float*)words.data();
   const int ncoll = bi[AGX_H_NCOLL];
   const int npart = h->particles ? h->cloth_nn : 0;
   if (ncoll + npart > AGX_RENDER_LIST) return fail(AGX_E_LIMIT, "agx_camera_set: more than 1,024 colliders and particles");
   std::vector<agx_render_coll> coll((size_t)ncoll);
   std::vector<float4> planes;
-  for (int c = 0; c < ncoll; c++) coll[c].genders = 3;
-  // a human collider is drawn for one gender only where the pair table says so: the B range of a group that has a female alternative is the
-  // male human's, the alternative the female's; a group that exists for one gender only (flag bits 3, 4) names that gender's human colliders
-  for (int g = 0; g < bi[AGX_H_NGROUP]; g++) {
-    const int32_t* G = bi + bi[AGX_H_OFF_GROUP] + g * AGX_G_STRIDE;
-    auto only = [&](int c0, int c1, int bits) { for (int c = c0 < 0 ? 0 : c0; c < c1 && c < ncoll; c++) if (bi[bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE + AGX_C_TAG] == AGX_TAG_HUMAN) coll[c].genders &= bits; };
-    if (G[AGX_G_B0F] >= 0) { only(G[AGX_G_B0], G[AGX_G_B1], 1); only(G[AGX_G_B0F], G[AGX_G_B1F], 2); }
-    for (int s = 0; s < 2; s++) if (G[AGX_G_FLAGS] & (8 << s)) { only(G[AGX_G_A0], G[AGX_G_A1], 1 << s); only(G[AGX_G_B0], G[AGX_G_B1], 1 << s); }
-  }
+  const std::vector<int> genders = collider_genders(bi);
+  for (int c = 0; c < ncoll; c++) coll[c].genders = genders[c];
   std::vector<agxhull::Plane> pl;
   for (int c = 0; c < ncoll; c++) {
     const int32_t* Ci = bi + bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE; const float* Cf = (const float*)Ci;
@@ -906,6 +930,80 @@ int agx_camera_garment(agx_handle h, int on) {
     cam->A.tris = dev; cam->A.ntri = (int)n; cam->A.garment = h->L.cloth; cam->A.cloth_words = h->L.cloth_words;
   }
   cam->garment = on != 0;
+  return AGX_OK;
+}
+
+// ---- closest points between collider pairs (csrc/agx_proximity.h, csrc/agx_proximity.hip): every check before any launch
+int agx_proximity_set(agx_handle h, const int32_t* pairs_host, int npairs, int nqueries) {
+  if (!h) return fail(AGX_E_ARG, "agx_proximity_set: null handle");
+  if (!pairs_host) return fail(AGX_E_ARG, "agx_proximity_set: null pair list");
+  if (npairs < 1) return fail(AGX_E_ARG, "agx_proximity_set: npairs must be at least 1");
+  if (nqueries < 1 || nqueries > AGX_PROX_MAX_QUERIES) return fail(AGX_E_ARG, "agx_proximity_set: nqueries outside 1..16");
+  if (npairs > AGX_PROX_MAX_PAIRS) return fail(AGX_E_LIMIT, "agx_proximity_set: more than 8,192 pairs");
+  std::vector<int> packed((size_t)npairs * 4);
+  for (int k = 0; k < npairs; k++) {
+    const int a = pairs_host[3 * k], b = pairs_host[3 * k + 1], q = pairs_host[3 * k + 2];
+    if (a < 0 || a >= h->ncoll || b < 0 || b >= h->ncoll) return fail(AGX_E_ARG, "agx_proximity_set: a collider index outside [0, ncoll)");
+    if (a == b) return fail(AGX_E_ARG, "agx_proximity_set: a pair of a collider with itself");
+    if (q < 0 || q >= nqueries) return fail(AGX_E_ARG, "agx_proximity_set: a query id outside [0, nqueries)");
+    packed[4 * k] = a; packed[4 * k + 1] = b; packed[4 * k + 2] = q; packed[4 * k + 3] = 0;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->prox) {      // first use: the per-collider flags and the frame table
+    std::vector<uint32_t> words;
+    { const int rc = download_blob(h, words); if (rc) return rc; }
+    const int32_t* bi = (const int32_t*)words.data(); const float* bf = (const float*)words.data();
+    const int ncoll = bi[AGX_H_NCOLL];
+    std::vector<int> flags = collider_genders(bi);
+    for (int c = 0; c < ncoll; c++) {
+      const int32_t* Ci = bi + bi[AGX_H_OFF_COLL] + c * AGX_C_STRIDE; const float* Cf = (const float*)Ci;
+      bool fin = isfinite(Cf[AGX_C_RADIUS]);
+      for (int k = 0; k < 6; k++) fin = fin && isfinite(Cf[AGX_C_AABB_C + k]);
+      const float* V = bf + bi[AGX_H_OFF_VERT] + 3 * Ci[AGX_C_VOFF];
+      for (int k = 0; k < 3 * Ci[AGX_C_NVERT]; k++) fin = fin && isfinite(V[k]);
+      if (fin && Ci[AGX_C_NVERT] >= 1) flags[c] |= AGX_PROX_FINITE;
+    }
+    agx_prox_s* P = new agx_prox_s();
+    memset(P, 0, sizeof *P);
+    h->prox = P;      // from here on agx_destroy releases it
+    P->ncoll = ncoll;
+    HIPCHK(hipMalloc(&P->frames, (size_t)h->L.n_envs * (ncoll > 0 ? ncoll : 1) * 12 * 4));
+    HIPCHK(hipMalloc(&P->cflags, (size_t)(ncoll > 0 ? ncoll : 1) * 4));
+    if (ncoll) HIPCHK(hipMemcpy(P->cflags, flags.data(), (size_t)ncoll * 4, hipMemcpyHostToDevice));
+    P->A.blob = h->L.blob; P->A.state = h->L.state; P->A.sw = h->L.sw; P->A.frames = P->frames; P->A.cflags = P->cflags;
+  }
+  agx_prox_s* P = h->prox;
+  if (npairs > P->pairs_cap) {      // (hipFree waits for the launches that still read the old list)
+    hipFree(P->pairs); P->pairs = nullptr; P->pairs_cap = 0; P->A.npairs = 0;
+    HIPCHK(hipMalloc(&P->pairs, (size_t)npairs * 16));
+    P->pairs_cap = npairs;
+  } else HIPCHK(hipDeviceSynchronize());      // a later call replaces the list: no launch may still read it
+  HIPCHK(hipMemcpy(P->pairs, packed.data(), (size_t)npairs * 16, hipMemcpyHostToDevice));
+  int G = 1; while (G < AGX_WAVE && (G < npairs || G < nqueries)) G <<= 1;
+  P->A.pairs = P->pairs; P->A.npairs = npairs; P->A.nqueries = nqueries; P->A.group = G;
+  return AGX_OK;
+}
+int agx_proximity_pairs(agx_handle h, int* npairs, int* nqueries) {
+  if (!h) return fail(AGX_E_ARG, "agx_proximity_pairs: null handle");
+  if (npairs) *npairs = h->prox ? h->prox->A.npairs : 0;
+  if (nqueries) *nqueries = h->prox && h->prox->A.npairs ? h->prox->A.nqueries : 0;
+  return AGX_OK;
+}
+int agx_proximity(agx_handle h, int env0, int count, float max_distance, float* records_dev, float* nearest_dev, void* stream) {
+  if (!h) return fail(AGX_E_ARG, "agx_proximity: null handle");
+  if (!h->prox || h->prox->A.npairs == 0) return fail(AGX_E_ARG, "agx_proximity: no pair list; call agx_proximity_set first");
+  if (env0 < 0 || count < 1 || count > h->L.n_envs || env0 > h->L.n_envs - count) return fail(AGX_E_ARG, "agx_proximity: [env0, env0 + count) is not a range of the handle's environments");
+  if (!isfinite(max_distance) || max_distance < 0.f) return fail(AGX_E_ARG, "agx_proximity: max_distance is negative or not finite");
+  if (!records_dev && !nearest_dev) return fail(AGX_E_ARG, "agx_proximity: both outputs are null");
+  if (((uintptr_t)records_dev | (uintptr_t)nearest_dev) & 15) return fail(AGX_E_ARG, "agx_proximity: an output is not 16-byte aligned");
+  HIPCHK(hipSetDevice(h->device));
+  agx_prox_s* P = h->prox;
+  h->V->collider_frames(h->L, (hipStream_t)stream, env0, count, P->frames + (size_t)env0 * P->ncoll * 12);      // stage A, into the query's own table
+  HIPCHK(hipGetLastError());
+  agx_prox_args A = P->A;
+  A.env0 = env0; A.count = count; A.max_distance = max_distance; A.records = records_dev; A.nearest = nearest_dev;
+  agx_launch_proximity((hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
   return AGX_OK;
 }
 

@@ -62,11 +62,36 @@ def _box(n, bound):
 
 class _Agent:
     """The attributes of the reference's Robot / Human / Tool objects that learn.py, env_viewer.py and user scripts read
-    (controllable_joint_indices, agent.py:21; Robot tables, robot.py:6-39).  Physics calls on them do not exist here -- but for the robot's
-    end-effector calls, _Robot below."""
+    (controllable_joint_indices, agent.py:21; Robot tables, robot.py:6-39).  Of the physics calls on them, get_closest_points is built (env.robot,
+    env.tool and env.human of a scalar env) and the robot's end-effector calls, _Robot below; get_contact_points and link frames are not."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+    def get_closest_points(self, agentB, distance=4.0, linkA=None, linkB=None):
+        """agent.py:118-130: (linkA, linkB, posA, posB, distance) lists, one entry per pair of a collider of this agent and a collider of
+        `agentB` (optionally of links linkA / linkB only) whose surfaces are closer than `distance`, in pair order; a negative distance is a
+        penetration.  Bullet reports per collision shape of its own bodies; this reports per collider of the model blob (spheres, capsules
+        and convex hulls with a margin: what the stepper collides), one closest point per collider pair, answered by the batched query of
+        assistive_gym_amd/proximity.py on the env's one environment."""
+        from .proximity import ProximityQuery
+        env, tag_a, tag_b = getattr(self, '_env', None), getattr(self, '_tag', None), getattr(agentB, '_tag', None)
+        if env is None or tag_a is None or tag_b is None:
+            raise NotImplementedError('get_closest_points: only between env.robot, env.tool and env.human')
+        key = (tag_a, tag_b, float(distance), linkA, linkB)
+        cache = env.__dict__.setdefault('_proximity_queries', {})
+        st = env._ensure_stepper()
+        if key not in cache or cache[key].stepper is not st:
+            cache[key] = ProximityQuery(st, [((tag_a, [linkA]) if linkA is not None else tag_a, (tag_b, [linkB]) if linkB is not None else tag_b)], distance)
+        q = cache[key]
+        out = q.closest()
+        st.synchronize()
+        kind = out['kind'][0].cpu().numpy()
+        dist, pa, pb = (out[k][0].cpu().numpy().astype(np.float64) for k in ('distance', 'point_a', 'point_b'))
+        link = [q.blob.collider(int(c))['link'] for c in range(q.blob.h['NCOLL'])]
+        hit = [k for k in range(len(q.pairs)) if kind[k] != 0]
+        return ([link[q.pairs[k, 0]] for k in hit], [link[q.pairs[k, 1]] for k in hit], [tuple(pa[k]) for k in hit], [tuple(pb[k]) for k in hit],
+                [float(dist[k]) for k in hit])
 
 
 class _EndEffector(int):
@@ -84,7 +109,7 @@ class _Robot(_Agent):
     """The robot of a scalar env: the attribute bag plus the end-effector calls of the reference's teleoperation loop (teleop_example.py:
     robot.get_pos_orient(robot.right_end_effector), robot.get_joint_angles(robot.right_arm_joint_indices), robot.ik(...)), answered by the
     stepper's agx_ee_pose / agx_ee_ik for the env's one environment.  The IK is the damped-least-squares iteration of host/kin.py in float32 on
-    the device, not Bullet's; a link other than an end effector, contacts and closest points are not built."""
+    the device, not Bullet's; the frame of a link other than an end effector and contacts are not built."""
 
     def _bind(self, env, base):
         from .model import compiler as L
@@ -109,7 +134,7 @@ class _Robot(_Agent):
 
     def _arm(self, link):
         if not isinstance(link, _EndEffector):
-            raise NotImplementedError('only the end effector is built: pass robot.right_end_effector / robot.left_end_effector (link frames, contacts and closest points of other links are not)')
+            raise NotImplementedError('only the end effector is built: pass robot.right_end_effector / robot.left_end_effector (link frames and contacts of other links are not)')
         return link.arm
 
     def _poses(self):
@@ -185,6 +210,8 @@ class AssistiveEnv(_Base):
         self.robot._bind(self, base)
         self.human = _Agent(controllable_joint_indices=hum_pb, controllable=self.coop)
         self.tool = _Agent()
+        for agent, tag in ((self.robot, 'robot'), (self.tool, 'tool'), (self.human, 'human')):      # what get_closest_points asks about
+            agent._env, agent._tag = self, tag
         self.camera_width, self.camera_height, self.view_matrix, self.projection_matrix = None, None, None, None
         self.seed(1001)                                                               # env.py:21,30
 

@@ -17,7 +17,7 @@ EXPORTS = ['agx_version', 'agx_last_error', 'agx_device_count', 'agx_lds_bytes_p
            'agx_synchronize', 'agx_selftest', 'agx_debug_layout', 'agx_variant_name', 'agx_overflow_count', 'agx_chunk_count', 'agx_set_env_offset', 'agx_check_collisions',
            'agx_comm_unique_id', 'agx_comm_init_rank', 'agx_comm_destroy', 'agx_allgather', 'agx_pack_step', 'agx_policy_act', 'agx_gae', 'agx_ee_arms', 'agx_ee_pose', 'agx_ee_ik',
            'agx_camera_set', 'agx_render', 'agx_collider_count', 'agx_collider_frames', 'agx_camera_colours',
-           'agx_camera_garment', 'agx_garment_faces', 'agx_camera_garment_colour']
+           'agx_camera_garment', 'agx_garment_faces', 'agx_camera_garment_colour', 'agx_proximity_set', 'agx_proximity_pairs', 'agx_proximity']
 
 
 class AgxError(RuntimeError):
@@ -47,6 +47,9 @@ def load():
         L.agx_camera_garment.argtypes = [C.c_void_p, C.c_int]
         L.agx_garment_faces.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
         L.agx_camera_garment_colour.argtypes = [C.c_void_p]
+        L.agx_proximity_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.agx_proximity_pairs.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.agx_proximity.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -319,6 +322,30 @@ class Stepper:
         if n.value:
             check(self.L.agx_garment_faces(self.h, C.byref(n), out.ctypes.data_as(C.c_void_p)), 'agx_garment_faces')
         return out
+
+    # ---- closest points between collider pairs (agx_proximity_set / agx_proximity, include/agx.h)
+    def proximity_set(self, pairs, nqueries=1):
+        """the pair list of the closest-point query: int32 [npairs, 3] rows (collider a, collider b, query id in [0, nqueries)); replaces an earlier list"""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        assert pairs.ndim == 2 and pairs.shape[1] == 3
+        check(self.L.agx_proximity_set(self.h, pairs.ctypes.data_as(C.c_void_p), int(pairs.shape[0]), int(nqueries)), 'agx_proximity_set')
+
+    def proximity_pairs(self):
+        """(pairs, queries) of the list that is set; (0, 0) before proximity_set"""
+        n, q = C.c_int(), C.c_int()
+        check(self.L.agx_proximity_pairs(self.h, C.byref(n), C.byref(q)), 'agx_proximity_pairs')
+        return n.value, q.value
+
+    def proximity(self, max_distance, records=None, nearest=None, env0=0, stream=0):
+        """agx_proximity of the environments [env0, env0 + count) into contiguous float32 device tensors records [count, npairs, 12] and nearest
+        [count, nqueries, 12] (either may be None; count is the first dimension): per record dist, point on A, point on B, normal from B towards A,
+        int32 kind, int32 pair index.  Only points closer than max_distance are reported (kind 0, dist = +inf otherwise)"""
+        outs = [x for x in (records, nearest) if x is not None]
+        assert all(x.is_contiguous() and x.dim() == 3 and x.shape[2] == 12 for x in outs) and len({int(x.shape[0]) for x in outs}) <= 1
+        npairs, nq = self.proximity_pairs()
+        assert (records is None or records.shape[1] == npairs) and (nearest is None or nearest.shape[1] == nq)
+        check(self.L.agx_proximity(self.h, int(env0), int(outs[0].shape[0]) if outs else 0, float(max_distance), records.data_ptr() if records is not None else None,
+                                   nearest.data_ptr() if nearest is not None else None, stream or None), 'agx_proximity')
 
     def settle(self, n_substeps, stream=0):
         check(self.L.agx_settle(self.h, C.c_int(n_substeps), C.c_void_p(stream)), 'agx_settle')

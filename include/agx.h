@@ -291,6 +291,37 @@ int agx_camera_garment(agx_handle h, int on);
 int agx_garment_faces(agx_handle h, int* count, int* host_tris);
 int agx_camera_garment_colour(float* out3);
 
+/* ---- closest points between collider pairs of the environments, on the device (csrc/agx_proximity.h, csrc/agx_proximity.hip).  The reference's
+ * Agent.get_closest_points(agentB, distance, linkA, linkB) (assistive_gym/envs/agents/agent.py:118-130) asks PyBullet for the points of two bodies
+ * closer than `distance`; here a query is a list of collider pairs of the model blob, answered for a range of environments in one call: the
+ * variant's frames kernel into a frame table of the query's own, then one kernel whose work item is one (environment, pair), a lane each, every
+ * lane running the narrowphase of the stepper (csrc/agx_gjk.h).
+ * A record is 12 words: 0 dist, the surface distance, negative when penetrating | 1-3 the point on A's surface, world | 4-6 the point on B's |
+ * 7-9 the unit normal from B towards A (as in the contact records, Bullet's contactNormalOnB) | 10 int32 kind | 11 int32 pair index.
+ *   kind 1, closest points: core = convex hull of the collider's vertices placed by its body's frame, d the distance of the cores, (ca, cb) their
+ *     closest points; n = (ca - cb) / d, dist = d - r_a - r_b, pa = ca - r_a n, pb = cb + r_b n.
+ *   kind 2, overlapping cores (closer than a micron counts): the direction of the blob's table with the smallest max_B(x.d) - min_A(x.d), the first
+ *     on ties; n that direction, dist = -that - r_a - r_b, pa = A's first vertex of smallest x.n, less r_a n, pb = pa - dist n.
+ *   kind 0, nothing reported: dist = +inf, words 1-9 zero -- dist >= max_distance (Bullet reports closer points only), a human collider that is
+ *     not of the environment's gender, a frame or a vertex that is not finite.  A NaN is never written.
+ *   A static world box (body AGX_BODY_WORLD, 8 vertices, tag TABLE or PLANE) is taken as the axis-aligned box it is, clipped to the other
+ *   collider's world box grown by a bound on their distance (exact: the box's nearest point is the clamp of a point of the other collider;
+ *   the bound does not look at max_distance, so a record is the same at every max_distance above its dist);
+ *   one point per pair, no face manifold.
+ * Nearest records: the same 12 words per (environment, query) -- a query is the subset of the pairs that carry its id: the record of smallest dist
+ *   among those with kind != 0, the lower pair index on a tie, word 11 the winning pair; none: kind 0, pair -1, dist = +inf.
+ * agx_proximity_set: the pair list [npairs][3] = collider a, collider b, query id, on the host.  The first call allocates the frame table; a later
+ *   call replaces the list.  agx_proximity_pairs: what is set (0, 0 before a set).
+ * agx_proximity: environments [env0, env0 + count) into records_dev [count][npairs][12] and nearest_dev [count][nqueries][12], float32 device arrays,
+ *   16-byte aligned, either of which may be NULL (not both).  Results are bit-reproducible and do not depend on the range asked for.
+ * AGX_E_ARG, with agx_last_error text, before any launch: a NULL handle or list, npairs < 1, nqueries outside 1..16, a collider index outside
+ * [0, ncoll), a == b, a query id outside [0, nqueries), agx_proximity before a set, a range outside the handle's environments, max_distance
+ * negative or not finite, both outputs NULL, an output that is not 16-byte aligned.  AGX_E_LIMIT: more than 8,192 pairs.
+ * Nothing here writes the state, garment or camera records. */
+int agx_proximity_set(agx_handle h, const int32_t* pairs_host, int npairs, int nqueries);
+int agx_proximity_pairs(agx_handle h, int* npairs, int* nqueries);
+int agx_proximity(agx_handle h, int env0, int count, float max_distance, float* records_dev, float* nearest_dev, void* stream);
+
 /* convenience wrappers with HOST buffers (copies included; not the timed path) */
 int agx_step_host(agx_handle h, const float* actions, float* obs, float* reward, uint8_t* done, float* info);
 int agx_observe_host(agx_handle h, float* obs);
